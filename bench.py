@@ -13,9 +13,15 @@ SURVEY.md 8(d) d2) before the timed region; every rank has its own images
 synchronisation between them inside the timed region (graph replay; the
 streams' stages overlap).  For N > 1 each sub-batch's keypoints are gathered
 to rank 0 over RCCL one step behind the compute (sift-gpu_amd/sift_dist.py),
-and the last step's gather is inside the timed region.  Stage times and the
-per-kernel rooflines come from a separate serial leg (one context, the whole
-batch, HIP events around every stage).
+and the last step's gather is inside the timed region.
+
+A plain run does only that: set-up, --warmup steps, --steps timed steps, the
+--dump-outputs files if asked for (what the last timed step computed, as .npy:
+see dump_outputs), and the one JSON line with the headline (`value`,
+`ms_per_step`, ...).  Everything below runs only with --full.
+
+Stage times and the per-kernel rooflines come from a separate serial leg (one
+context, the whole batch, HIP events around every stage).
 
 Outside the timed region rank 0 checks its image 0 (seed 0) -- and seeds 31
 and 63 at the default shape -- against the CPU path's SHA-256 digests
@@ -25,7 +31,8 @@ single-image latency (hipGraph replay, 4 octaves), configs[4] (one 8K image,
 output checked, pyramid rooflines at C5), the knnMatch leg, and the CPU
 baseline (oracle, 1 thread + image-parallel on the host's cores).
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  At N > 1 without a
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full]
+[--dump-outputs DIR].  At N > 1 without a
 launcher, bench.py starts `python -m torch.distributed.run --nproc-per-node N
 --master-addr 127.0.0.1 ... bench.py <same args>` as a child process (one rank
 per GPU, RCCL) and exits with its code; under a launcher WORLD_SIZE must equal
@@ -82,8 +89,18 @@ def parse():
     p.add_argument("--no-multi", action="store_true", help="skip the C-ABI multi-GPU (sift_multi_*) leg")
     p.add_argument("--only", default=None, choices=[None, "exact", "fast", "single", "8k", "multi"],
                    help="profiling runs: time only this leg")
-    p.add_argument("--profile-json", default=None, help="also write per-stage stats here")
-    return p.parse_args()
+    p.add_argument("--profile-json", default=None, help="also write per-stage stats here (needs --full)")
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline: its output check, the serial profiled leg (stage times, "
+                        "rooflines), the CPU baselines and the fast / match / single / 8k / multi legs "
+                        "(--only LEG implies it)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last step computed as DIR/<name>.npy")
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    a.full = a.full or a.only is not None
+    return a
 
 
 # ---- CPU baseline (oracle = C restatement of the reference path) ------------
@@ -574,6 +591,11 @@ class Part:
             with torch.cuda.stream(self.stream):
                 self.runner.flush()
 
+    def last_bufs(self):
+        """The (kpts, desc, offs) the last timed step wrote: with a gather,
+        step i of a leg uses slot i % 2."""
+        return self.bufs[(self.env.a.steps - 1) % 2 if self.runner is not None else 0]
+
     def close(self):
         self.ctx.close()
 
@@ -595,9 +617,11 @@ class Env:
         self.parts = [Part(self, B * s // S, B * (s + 1) // S - B * s // S,
                            torch.cuda.Stream() if S > 1 else torch.cuda.current_stream(), self.gathering)
                       for s in range(S)]
-        self.serial = Part(self, 0, B, torch.cuda.current_stream(), False)
-        self.serial.ctx.synth_images(self.imgs.data_ptr(), B, self.R, self.C, self.C, self.R * self.C,
-                                     seed_base=self.seed_base)
+        # the serial (profiled) part holds a whole-batch context: --full only
+        self.serial = Part(self, 0, B, torch.cuda.current_stream(), False) if a.full else None
+        for p in self.parts:   # image b of this rank is seed seed_base + b, whichever part generates it
+            p.ctx.synth_images(self.imgs[p.b0].data_ptr(), p.nb, self.R, self.C, self.C, self.R * self.C,
+                               seed_base=self.seed_base + p.b0)
         torch.cuda.synchronize()
 
     def shard_batches(self, nb):
@@ -679,20 +703,68 @@ class Env:
                         "those transfer groups summed over the timed leg, overlapped with compute"}
 
     def close(self):
-        for p in self.parts + [self.serial]:
+        for p in self.parts + ([self.serial] if self.serial is not None else []):
             p.close()
 
 
+DUMP_BYTES = 48 << 20   # --dump-outputs: budget for the sampled records (the whole dump stays under 64 MB)
+
+
+def dump_outputs(path, env):
+    """--dump-outputs: what the timed parts hold after the last timed step,
+    as a caller of sift_detect_compute_batch receives it.  offsets.npy: the
+    B + 1 per-image keypoint offsets of the whole batch.  The keypoint
+    records (x, y, size, angle, response as stored; octave, class_id as
+    numbers) and the 128-float descriptors are written for a fixed sample of
+    whole images (seeded order, as many as fit DUMP_BYTES; of an image that
+    alone is larger, its leading rows): sample_images.npy names them,
+    sample_offsets.npy delimits their rows in keypoints.npy / descriptors.npy."""
+    os.makedirs(path, exist_ok=True)
+    counts, images = [], {}
+    for p in env.parts:
+        k, d, o = p.last_bufs()
+        o = o.cpu().numpy().astype(np.int64)
+        counts.extend(np.diff(o).tolist())
+        for b in range(p.nb):
+            images[p.b0 + b] = (k, d, int(o[b]), int(o[b + 1]))
+    max_rows = DUMP_BYTES // (7 * 8 + siftgpu.DESC_LEN * 4)
+    chosen, rows = [], 0
+    for b in np.random.default_rng(0).permutation(env.B).tolist():
+        if rows + counts[b] > max_rows:
+            break
+        chosen.append(b)
+        rows += counts[b]
+    kps, descs, soffs = [], [], [0]
+    for b in chosen or [0]:
+        k, d, lo, hi = images[b]
+        hi = min(hi, lo + max_rows)
+        rec = k[lo:hi].cpu().numpy()
+        kp = np.empty((hi - lo, 7), dtype=np.float64)
+        kp[:, :5] = rec[:, :5].view(np.float32)
+        kp[:, 5:] = rec[:, 5:]
+        kps.append(kp)
+        descs.append(d[lo:hi].cpu().numpy().astype(np.float32, copy=False))
+        soffs.append(soffs[-1] + hi - lo)
+    np.save(os.path.join(path, "offsets.npy"), np.concatenate([[0], np.cumsum(counts)]).astype(np.float64))
+    np.save(os.path.join(path, "sample_images.npy"), np.asarray(chosen or [0], dtype=np.float64))
+    np.save(os.path.join(path, "sample_offsets.npy"), np.asarray(soffs, dtype=np.float64))
+    np.save(os.path.join(path, "keypoints.npy"), np.concatenate(kps))
+    np.save(os.path.join(path, "descriptors.npy"), np.concatenate(descs))
+
+
 def run_exact(env):
-    """The headline: the exact leg (timed streams) + its output check + the
-    serial profiled leg (stage times, rooflines)."""
+    """The headline: the exact leg (timed streams); with --full its output
+    check and the serial profiled leg (stage times, rooflines) as well."""
     exact = env.leg(env.parts, 0)
-    verified, failed = [], []
-    if env.rank == 0:
+    if env.a.dump_outputs and env.rank == 0:
+        dump_outputs(env.a.dump_outputs, env)
+    verified = failed = prof = None
+    if env.a.full and env.rank == 0:
         verified, failed = verify_outputs([(p.b0, p.nb) + p.bufs[0] for p in env.parts], env.R, env.C,
                                           env.octaves, env.seed_base)
     gather = env.gather_evidence(exact[0]) if env.gathering else None
-    prof = env.leg([env.serial], siftgpu.SIFT_FLAG_PROFILE)
+    if env.a.full:
+        prof = env.leg([env.serial], siftgpu.SIFT_FLAG_PROFILE)
     return {"exact": exact, "prof": prof, "verified": verified, "failed": failed, "gather": gather}
 
 
@@ -712,14 +784,12 @@ def run_match(env):
     return match_leg(s.ctx, env.a, s.bufs[0][1], s.bufs[0][2])
 
 
-def exact_block(a, world, B, R, C, S, res, tr):
-    """The headline fields from run_exact's result."""
+def profile_block(a, world, B, R, C, res, tr):
+    """--full: stage times and rooflines from run_exact's serial profiled leg."""
     out = {}
-    dt, _, kp_total_step = res["exact"]
-    pdt, stats, _ = res["prof"]   # stage times / rooflines: the serial profiled leg
-    verified, failed = res["verified"], res["failed"]
+    kp_total_step = res["exact"][2]
+    pdt, stats, _ = res["prof"]
     mpix = world * B * R * C * a.steps / 1e6
-    value = mpix / dt
 
     # roofline of the dominant kernel: the exact octave blur -- octave 0
     # in scatter form (blur_sym_kernel) when the library chose it for
@@ -756,12 +826,44 @@ def exact_block(a, world, B, R, C, S, res, tr):
     pyr_ms = sum(stats[k]["ms"] for k in ("blur_base", "blur_octave", "blur_octave_sym", "decimate", "dog")
                  if k in stats)
     pyr_bytes = 24.0 * sum(sum((R >> o) * (C >> o) for o in range(a.octaves)) for _ in range(B)) * a.steps
+    out.update({
+        "roofline": roof,
+        "roofline_octaves_2d_tiles": roof_gather,
+        "pyramid": {"ms_per_step": round(pyr_ms / a.steps, 3),
+                    "algorithmic_GBs": round(pyr_bytes / (pyr_ms * 1e-3) / 1e9, 1) if pyr_ms else None,
+                    "note": "B_pyr = 24 B x sum of octave pixels (1 read + 5 plane writes), SURVEY.md 8(d)"},
+        "stages_ms_per_step": {k: round(v["ms"] / a.steps, 3) for k, v in stats.items()},
+        "serial_leg": {"ms_per_step": round(pdt / a.steps * 1e3, 3),
+                       "Mpix_per_s": round(mpix / pdt, 2),
+                       "note": "one context, the whole batch on one stream, HIP events around every "
+                               "stage (SIFT_FLAG_PROFILE, no graph): the source of stages_ms_per_step, "
+                               "roofline and descriptor; value is the streams leg (graph replay, no "
+                               "events)"},
+    })
+    d = stats.get("descriptor")
+    if d:
+        out["descriptor"] = {"ms_per_step": round(d["ms"] / a.steps, 3),
+                             "keypoints_per_s_kernel": round(kp_total_step / world * a.steps /
+                                                             (d["ms"] * 1e-3), 1),
+                             "roofline": descriptor_roofline(tr, d)}
+    return out
+
+
+def exact_block(a, world, B, R, C, S, res, tr):
+    """The headline fields from run_exact's result; with --full the output
+    check's verdict in front and profile_block's fields behind them."""
+    out = {}
+    dt, _, kp_total_step = res["exact"]
+    verified, failed = res["verified"], res["failed"]
+    mpix = world * B * R * C * a.steps / 1e6
+    value = mpix / dt
     gathering = res.get("gather") is not None
     backend = (res.get("gather") or {}).get("backend")
-    out.update({
+    if verified is not None:
         # first after the metric: the driver's record keeps only the line's head
-        "output_verified": bool(verified) and not failed,
-        "output_verified_seeds": verified,
+        out.update({"output_verified": bool(verified) and not failed,
+                    "output_verified_seeds": verified})
+    out.update({
         "value": round(value, 2),
         "unit": "Mpix/s",
         "n_gpus": world,
@@ -782,29 +884,13 @@ def exact_block(a, world, B, R, C, S, res, tr):
                                    if gathering else "")},
         "keypoints_per_s": round(kp_total_step * a.steps / dt, 1),
         "keypoints_per_step": int(kp_total_step),
-        "roofline": roof,
-        "roofline_octaves_2d_tiles": roof_gather,
-        "pyramid": {"ms_per_step": round(pyr_ms / a.steps, 3),
-                    "algorithmic_GBs": round(pyr_bytes / (pyr_ms * 1e-3) / 1e9, 1) if pyr_ms else None,
-                    "note": "B_pyr = 24 B x sum of octave pixels (1 read + 5 plane writes), SURVEY.md 8(d)"},
-        "stages_ms_per_step": {k: round(v["ms"] / a.steps, 3) for k, v in stats.items()},
-        "serial_leg": {"ms_per_step": round(pdt / a.steps * 1e3, 3),
-                       "Mpix_per_s": round(mpix / pdt, 2),
-                       "note": "one context, the whole batch on one stream, HIP events around every "
-                               "stage (SIFT_FLAG_PROFILE, no graph): the source of stages_ms_per_step, "
-                               "roofline and descriptor; value is the streams leg (graph replay, no "
-                               "events)"},
     })
+    if res["prof"] is not None:
+        out.update(profile_block(a, world, B, R, C, res, tr))
     if failed:
         out["output_failed_seeds"] = failed
     if gathering:
         out["gather"] = res["gather"]
-    d = stats.get("descriptor")
-    if d:
-        out["descriptor"] = {"ms_per_step": round(d["ms"] / a.steps, 3),
-                             "keypoints_per_s_kernel": round(kp_total_step / world * a.steps /
-                                                             (d["ms"] * 1e-3), 1),
-                             "roofline": descriptor_roofline(tr, d)}
     return out
 
 
@@ -922,7 +1008,7 @@ CPU_JSON_ENV = "SIFT_BENCH_CPU_JSON"
 
 
 def wants_cpu_legs(a) -> bool:
-    return not a.no_cpu_baseline and a.only is None
+    return a.full and not a.no_cpu_baseline and a.only is None
 
 
 def save_cpu_legs(cpu, errors, path):
@@ -1038,16 +1124,17 @@ def main():
     else:
         torch.cuda.set_device(0)
     env = Env(a, world, rank)
-    want = (lambda leg_name: a.only in (None, leg_name))
     res = {}
-    if want("exact"):
+    if a.only in (None, "exact"):
         res["exact"] = run_exact(env)   # the headline: not guarded
+    # every further leg is a run of its own: --full (or --only LEG) asks for it
+    want = (lambda leg_name: a.full and a.only in (None, leg_name))
     # the fast leg only at N = 1: with collectives inside, a failure caught on
     # one rank would leave the others waiting in that collective;
     # the multi-GPU line is the exact path's
     if not a.no_fast and want("fast") and world == 1:
         res["fast"] = guarded(errors, "fast", run_fast, env)
-    if not (a.no_match or rank != 0 or env.B < 2 or res.get("exact") is None):
+    if not (a.no_match or rank != 0 or env.B < 2 or res.get("exact") is None or not a.full):
         res["match"] = guarded(errors, "match", run_match, env)
     if rank == 0 and world == 1 and not a.no_single and want("single"):
         res["single"] = guarded(errors, "single", single_image_leg, env.R, env.C, a.steps, a.warmup)
@@ -1063,7 +1150,7 @@ def main():
         if rehearsal():
             out["distributed"]["rehearsal"] = ("SIFT_BENCH_SHARE_GPU=1: ranks share devices; not a "
                                                "multi-GPU measurement")
-        if a.profile_json and res.get("exact") is not None:
+        if a.profile_json and res.get("exact") is not None and res["exact"]["prof"] is not None:
             with open(a.profile_json, "w") as f:
                 json.dump(res["exact"]["prof"][1], f, indent=1)
         print(json.dumps(out), flush=True)
@@ -1082,11 +1169,11 @@ def main():
 
 
 def output_check_passed(a, out, res) -> bool:
-    """The headline's output check must pass for the run to pass: at the
+    """The headline's output check (--full) must pass for the run to pass: at the
     golden shape every checked seed must equal the CPU path's digest (count,
     keypoint bytes, descriptor bytes) and none may fail.  Shapes without
     digests (--rows/--cols/--octaves changed) are not checked."""
-    if res.get("exact") is None:
+    if res.get("exact") is None or res["exact"]["verified"] is None:   # no headline, or no --full
         return True
     if a.octaves != 5 or (a.rows, a.cols) != (1080, 1920):
         return True

@@ -6,6 +6,7 @@ import subprocess
 import sys
 import types
 
+import numpy as np
 import pytest
 
 import os
@@ -59,7 +60,7 @@ def test_line_survives_failing_legs(bench, monkeypatch, capsys):
     monkeypatch.setattr(bench, "single_image_leg", boom)
     monkeypatch.setattr(bench, "eightk_leg", boom)
     monkeypatch.setattr(bench, "c_abi_multi_leg", boom)
-    out = _run(bench, monkeypatch, capsys, [])
+    out = _run(bench, monkeypatch, capsys, ["--full"])
     assert out["value"] > 0 and out["unit"] == "Mpix/s" and out["n_gpus"] == 1
     assert out["roofline"]["kernel"] == "blur_sym_kernel" and out["roofline"]["frac"] > 0
     assert out["cpu_baseline"]["value"] == 0.6 and "speedup_vs_cpu_1thread" in out
@@ -74,7 +75,7 @@ def test_line_survives_failing_cpu_leg(bench, monkeypatch, capsys):
     monkeypatch.setattr(bench, "cpu_baseline_parallel", boom)
     for leg in ("run_fast", "run_match", "single_image_leg", "eightk_leg", "c_abi_multi_leg"):
         monkeypatch.setattr(bench, leg, lambda *a, **k: None)
-    out = _run(bench, monkeypatch, capsys, [])
+    out = _run(bench, monkeypatch, capsys, ["--full"])
     assert out["value"] > 0 and out["cpu_baseline"]["value"] == 0.6
     assert "cpu_baseline_gpu_share" not in out and "cpu leg hung" in out["leg_errors"]["cpu_baseline_gpu_share"]
 
@@ -159,7 +160,7 @@ def test_shared_gpu_rehearsal_launches_past_the_device_count(bench, monkeypatch)
 def test_line_carries_world_and_launcher(bench, monkeypatch, capsys):
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     _quiet_legs(bench, monkeypatch)
-    out = _run(bench, monkeypatch, capsys, ["--no-cpu-baseline"])
+    out = _run(bench, monkeypatch, capsys, ["--full", "--no-cpu-baseline"])
     assert out["distributed"] == {"world_size": 1, "backend": None, "launcher": "none"}
     keys = list(out)
     assert keys.index("output_verified") < keys.index("value") < 4
@@ -171,7 +172,7 @@ def test_failed_output_check_fails_the_run(bench, monkeypatch, capsys):
     monkeypatch.setattr(bench, "run_exact", lambda env: {"exact": (0.1, {}, 800000.0),
                                                          "prof": (0.12, _stats(), 0.0),
                                                          "verified": [0, 63], "failed": [31], "gather": None})
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--no-cpu-baseline"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
     with pytest.raises(SystemExit) as ex:
         bench.main()
     assert ex.value.code == 4
@@ -185,7 +186,7 @@ def test_unverified_without_failures_fails_the_run(bench, monkeypatch, capsys):
     monkeypatch.setattr(bench, "run_exact", lambda env: {"exact": (0.1, {}, 800000.0),
                                                          "prof": (0.12, _stats(), 0.0),
                                                          "verified": [], "failed": [], "gather": None})
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--no-cpu-baseline"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
     with pytest.raises(SystemExit) as ex:
         bench.main()
     assert ex.value.code == 4
@@ -201,13 +202,13 @@ def test_gpu_error_flag_by_exception_type(bench, monkeypatch, capsys):
     def chip(*a, **k):
         raise RuntimeError("relationship with the chip went wrong")
     monkeypatch.setattr(bench, "single_image_leg", chip)
-    out = _run(bench, monkeypatch, capsys, ["--no-cpu-baseline"])
+    out = _run(bench, monkeypatch, capsys, ["--full", "--no-cpu-baseline"])
     assert "chip" in out["leg_errors"]["single"]
 
     def hip(*a, **k):
         raise siftgpu.SiftError("sift_sync", siftgpu.SIFT_E_HIP, "illegal address")
     monkeypatch.setattr(bench, "single_image_leg", hip)
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--no-cpu-baseline"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
     with pytest.raises(SystemExit) as ex:
         bench.main()
     assert ex.value.code == 3
@@ -218,7 +219,7 @@ def test_line_survives_failing_block(bench, monkeypatch, capsys):
     monkeypatch.setattr(bench, "run_fast", lambda env: ((0.05, {}, 1.0), None))
     for leg in ("run_match", "single_image_leg", "eightk_leg", "c_abi_multi_leg"):
         monkeypatch.setattr(bench, leg, lambda *a, **k: None)
-    out = _run(bench, monkeypatch, capsys, ["--no-cpu-baseline"])
+    out = _run(bench, monkeypatch, capsys, ["--full", "--no-cpu-baseline"])
     assert out["value"] > 0 and "error" in out["fast_mode"]
 
 
@@ -239,7 +240,7 @@ def test_launcher_cpu_legs_reach_rank0_line(bench, monkeypatch, capsys, tmp_path
         return subprocess.CompletedProcess(cmd, 0)
     monkeypatch.setattr(bench.subprocess, "run", fake_run)
     monkeypatch.setattr(bench, "Env", lambda *a, **k: pytest.fail("the launcher touched the GPU"))
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--full"])
     with pytest.raises(SystemExit) as ex:
         bench.main()
     assert ex.value.code == 0
@@ -263,7 +264,7 @@ def test_launcher_cpu_legs_reach_rank0_line(bench, monkeypatch, capsys, tmp_path
     for k, v in (("WORLD_SIZE", "2"), ("RANK", "0"), ("LOCAL_RANK", "0"), (bench.CPU_JSON_ENV, str(cpu_file)),
                  ("SIFT_BENCH_SHARE_GPU", "1"), ("SIFT_BENCH_DIST_BACKEND", "gloo")):
         monkeypatch.setenv(k, v)
-    out = _run(bench, monkeypatch, capsys, ["--gpus", "2"])
+    out = _run(bench, monkeypatch, capsys, ["--gpus", "2", "--full"])
     assert out["n_gpus"] == 2 and out["cpu_baseline"]["value"] == 0.6
     assert out["speedup_vs_cpu_1thread"]["Mpix/s"] > 0
     assert out["leg_errors"]["cpu_baseline_gpu_share"] == "canned failure"
@@ -276,5 +277,127 @@ def test_launcher_cpu_legs_reach_rank0_line(bench, monkeypatch, capsys, tmp_path
         "value": 0.7, "unit": "Mpix/s", "cores": threads, "kind": "port", "keypoints_per_s": 4100.0,
         "sample": "canned"})
     gather["backend"] = "nccl"
-    out = _run(bench, monkeypatch, capsys, ["--gpus", "2"])
+    out = _run(bench, monkeypatch, capsys, ["--gpus", "2", "--full"])
     assert out["cpu_baseline"]["value"] == 0.7 and "RCCL" in out["config"]["parallelism"]
+
+
+class _FakePart:
+    """A timed part's buffers on the host: image b has counts[b] keypoints,
+    each record and descriptor row numbered so a row can be recognised."""
+
+    def __init__(self, b0, counts, row0):
+        import torch
+        self.b0, self.nb = b0, len(counts)
+        n = sum(counts)
+        rows = np.arange(row0, row0 + n)
+        rec = np.zeros((n + 3, 7), np.int32)   # capacity beyond the results, as in the bench
+        rec[:n, :5] = (rows[:, None] + np.arange(5) / 8).astype(np.float32).view(np.int32)
+        rec[:n, 5] = rows & 255
+        rec[:n, 6] = -1
+        desc = np.zeros((n + 3, 128), np.float32)
+        desc[:n] = rows[:, None] + np.arange(128) / 128
+        offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        self._bufs = tuple(torch.from_numpy(x) for x in (rec, desc, offs))
+
+    def last_bufs(self):
+        return self._bufs
+
+
+def _fake_env(counts, split):
+    env = types.SimpleNamespace(B=len(counts))
+    env.parts = [_FakePart(0, counts[:split], 0), _FakePart(split, counts[split:], sum(counts[:split]))]
+    return env
+
+
+def _load_dump(path):
+    names = sorted(os.listdir(path))
+    arrs = {n[:-4]: np.load(os.path.join(path, n), allow_pickle=False) for n in names}
+    assert all(n.endswith(".npy") for n in names)
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    return arrs
+
+
+def test_dump_outputs_whole_batch(bench, tmp_path):
+    """--dump-outputs: everything fits, so every image's rows are written,
+    record fields and descriptors as the parts hold them."""
+    counts = [3, 0, 5, 2, 4]
+    bench.dump_outputs(str(tmp_path / "d"), _fake_env(counts, 2))
+    d = _load_dump(tmp_path / "d")
+    assert d["offsets"].tolist() == [0, 3, 3, 8, 10, 14]
+    imgs = d["sample_images"].astype(int).tolist()
+    assert sorted(imgs) == [0, 1, 2, 3, 4]
+    so = d["sample_offsets"].astype(int)
+    assert np.diff(so).tolist() == [counts[b] for b in imgs]
+    assert d["keypoints"].shape == (14, 7) and d["descriptors"].shape == (14, 128)
+    for i, b in enumerate(imgs):
+        rows = np.arange(d["offsets"][b], d["offsets"][b + 1])
+        k = d["keypoints"][so[i]:so[i + 1]]
+        assert np.array_equal(k[:, 0], rows) and np.array_equal(k[:, 4], rows + 0.5)
+        assert np.array_equal(k[:, 5], rows.astype(int) & 255) and np.all(k[:, 6] == -1)
+        assert np.array_equal(d["descriptors"][so[i]:so[i + 1], 0], rows.astype(np.float32))
+    # the same outputs give the same files
+    bench.dump_outputs(str(tmp_path / "e"), _fake_env(counts, 2))
+    e = _load_dump(tmp_path / "e")
+    assert d.keys() == e.keys() and all(np.array_equal(d[k], e[k]) for k in d)
+
+
+def test_dump_outputs_samples_a_large_batch(bench, monkeypatch, tmp_path):
+    """Over the byte budget: whole images in a fixed order while they fit,
+    and the leading rows of one image that alone is too large."""
+    row_bytes = 7 * 8 + 128 * 4
+    counts = [6, 7, 5, 8, 6, 7]
+    monkeypatch.setattr(bench, "DUMP_BYTES", 15 * row_bytes)
+    bench.dump_outputs(str(tmp_path / "d"), _fake_env(counts, 3))
+    d = _load_dump(tmp_path / "d")
+    imgs = d["sample_images"].astype(int).tolist()
+    assert 1 <= len(imgs) < len(counts) and len(set(imgs)) == len(imgs)
+    assert d["offsets"].astype(int).tolist() == np.concatenate([[0], np.cumsum(counts)]).tolist()
+    assert len(d["keypoints"]) == len(d["descriptors"]) == sum(counts[b] for b in imgs) <= 15
+    assert sum(a.nbytes for a in d.values()) <= 15 * row_bytes + 8 * (len(counts) + 1 + 2 * len(imgs) + 1)
+    first = d["keypoints"][:counts[imgs[0]], 0]
+    assert np.array_equal(first, np.arange(counts[imgs[0]]) + d["offsets"][imgs[0]])
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 * row_bytes)
+    bench.dump_outputs(str(tmp_path / "e"), _fake_env(counts, 3))
+    e = _load_dump(tmp_path / "e")
+    assert e["sample_images"].tolist() == [0] and e["sample_offsets"].tolist() == [0, 4]
+    assert np.array_equal(e["keypoints"][:, 0], np.arange(4))
+
+
+def test_plain_run_times_the_headline_only(monkeypatch, capsys, tmp_path):
+    """Without --full: the timed leg, the dump and the line -- no output
+    check, no profiled leg, no CPU baseline, no further leg; --steps is the
+    number of timed steps and ms_per_step their mean."""
+    calls = []
+
+    class PlainEnv:
+        def __init__(self, a, world, rank):
+            self.a, self.world, self.rank = a, world, rank
+            self.B, self.R, self.C, self.S, self.octaves, self.seed_base = a.batch, a.rows, a.cols, 2, a.octaves, 0
+            self.gathering, self.serial = False, None
+            fake = _fake_env([3, 0, 5, 2, 4], 2)
+            self.parts, self.B = fake.parts, fake.B
+
+        def leg(self, ps, flags):
+            calls.append((len(ps), flags, self.a.steps, self.a.warmup))
+            return 0.007 * self.a.steps, {}, 14.0
+
+        def close(self):
+            pass
+    import torch
+    import bench   # not the fixture: this test runs the real run_exact
+    monkeypatch.setattr(torch.cuda, "set_device", lambda *a, **k: None)
+    monkeypatch.setattr(bench, "Env", PlainEnv)
+    for name in ("cpu_baseline", "cpu_baseline_parallel", "verify_outputs", "run_fast", "run_match",
+                 "single_image_leg", "eightk_leg", "c_abi_multi_leg", "match_cpu_baseline"):
+        monkeypatch.setattr(bench, name, lambda *a, _n=name, **k: pytest.fail(f"a plain run called {_n}"))
+    out = _run(bench, monkeypatch, capsys, ["--gpus", "1", "--steps", "7", "--warmup", "3",
+                                            "--dump-outputs", str(tmp_path / "d")])
+    assert calls == [(2, 0, 7, 3)]
+    assert out["metric"] == bench.METRIC and out["unit"] == "Mpix/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32" and out["steps"] == 7 and out["warmup"] == 3 and out["n_gpus"] == 1
+    assert out["ms_per_step"] == 7.0
+    assert out["value"] == round(5 * 1080 * 1920 / 1e6 / 0.007, 2)
+    for moved in ("output_verified", "roofline", "stages_ms_per_step", "serial_leg", "descriptor", "cpu_baseline",
+                  "fast_mode", "match", "single_image", "image_8k", "c_abi_multi", "leg_errors"):
+        assert moved not in out, moved
+    assert _load_dump(tmp_path / "d")["offsets"].tolist() == [0, 3, 3, 8, 10, 14]

@@ -255,3 +255,46 @@ def test_graph_cache_rotating_buffers(siftgpu, oracle):
         caps, upd, inst = ctx.graph_stats()
     assert inst == 1, (caps, upd, inst)          # one shape: one executable
     assert upd == caps - 1 == len(order) - 1, (caps, upd, inst)  # every other call patched it
+
+
+def test_bench_plain_run_dumps_its_outputs(siftgpu, oracle, monkeypatch, capsys, tmp_path):
+    """bench.py without --full, in this process, on a small batch split
+    unevenly over its two streams (2 + 3 images): the line's headline fields,
+    and --dump-outputs holding the timed path's keypoints and descriptors --
+    bit for bit the CPU path's for every image (all fit the sample)."""
+    import json
+    import os
+    import sys
+    from conftest import ROOT
+    monkeypatch.syspath_prepend(ROOT)
+    import bench
+    B, r, c = 5, 96, 128
+    out_dir = tmp_path / "dump"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B),
+                                      "--rows", str(r), "--cols", str(c), "--dump-outputs", str(out_dir)])
+    bench.main()
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["metric"] == bench.METRIC and line["unit"] == "Mpix/s" and line["dtype"] == "f32"
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+    # value = pixels of one step / ms_per_step, up to the rounding of both (3 and 2 decimals)
+    assert abs(line["value"] - B * r * c / 1e6 / (line["ms_per_step"] * 1e-3)) <= \
+        0.0006 / line["ms_per_step"] * line["value"] + 0.01
+    assert "cpu_baseline" not in line and "stages_ms_per_step" not in line and "single_image" not in line
+    d = {n[:-4]: np.load(out_dir / n, allow_pickle=False) for n in os.listdir(out_dir)}
+    assert set(d) == {"offsets", "sample_images", "sample_offsets", "keypoints", "descriptors"}
+    assert d["descriptors"].dtype == np.float32 and all(d[k].dtype == np.float64 for k in d if k != "descriptors")
+    ref = [oracle.sift(oracle.synth_image(b, r, c)) for b in range(B)]
+    assert d["offsets"].tolist() == np.concatenate([[0], np.cumsum([len(k) for k, _ in ref])]).tolist()
+    assert line["keypoints_per_step"] == d["offsets"][-1] > 0
+    imgs = d["sample_images"].astype(int).tolist()
+    so = d["sample_offsets"].astype(int)
+    assert sorted(imgs) == list(range(B))
+    for i, b in enumerate(imgs):
+        kr, dr = ref[b]
+        k = d["keypoints"][so[i]:so[i + 1]]
+        assert len(k) == len(kr), f"image {b}"
+        for j, f in enumerate(siftgpu.KEYPOINT_DTYPE.names):
+            assert_bits_equal(k[:, j].astype(kr[f].dtype), kr[f], f"image {b} keypoint field {f}")
+        assert_bits_equal(d["descriptors"][so[i]:so[i + 1]], dr, f"image {b} descriptors")

@@ -61,7 +61,7 @@ import sys, json
 for l in sys.stdin:
     d = json.loads(l); print(d['tag'], d['total_ms'], json.dumps(d['stages_ms']))" ;;
       bench)
-        env $ENVS timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-single --no-8k --no-match --no-fast \
+        env $ENVS timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-single --no-8k --no-match --no-fast \
           --steps 10 $ARGS > $f.json 2> $f.err || { echo "bench $v failed"; tail -5 $f.err; exit 1; }
         python3 -c "
 import json, sys
@@ -69,14 +69,14 @@ d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(sys.argv[2], d['value'], d['ms_per_step'], 'serial', d['serial_leg']['ms_per_step'], 'verified', d['output_verified'],
       'desc', d['stages_ms_per_step'].get('descriptor'))" $f.json "$v" ;;
       single)
-        env $ENVS timeout -k 10 300 python3 bench.py --only single --steps 20 --warmup 5 $ARGS > $f.json 2> $f.err \
+        env $ENVS timeout -k 10 300 python3 bench.py --full --only single --steps 20 --warmup 5 $ARGS > $f.json 2> $f.err \
           || { echo "single $v failed"; tail -5 $f.err; exit 1; }
         python3 -c "
 import json, sys
 s = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]).get('single_image') or {}
 print(sys.argv[2], s.get('latency_ms'), s.get('device_no_graph_ms'), 'verified', s.get('output_verified'))" $f.json "$v" ;;
       8k)
-        env $ENVS timeout -k 10 200 python3 bench.py --only 8k --steps 5 --warmup 2 $ARGS > $f.json 2> $f.err \
+        env $ENVS timeout -k 10 200 python3 bench.py --full --only 8k --steps 5 --warmup 2 $ARGS > $f.json 2> $f.err \
           || { echo "8k $v failed"; tail -5 $f.err; exit 1; }
         python3 -c "
 import json, sys

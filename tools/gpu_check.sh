@@ -14,7 +14,7 @@ tail -1 $O/pytest.log
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 \
   || { tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err || { echo "bench failed rc=$?"; tail -5 $O/bench.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench failed rc=$?"; tail -5 $O/bench.err; exit 1; }
 python3 -c "
 import json; d = json.loads(open('$O/bench.json').read().strip().splitlines()[-1])
 print('value', d['value'], 'ms', d['ms_per_step'], 'verified', d['output_verified'], 'desc', d['stages_ms_per_step'].get('descriptor'))

@@ -258,6 +258,68 @@ int sift_knn_match_l1(sift_ctx* ctx, const float* query, int n_query, const floa
 int sift_knn_match_l1_device(sift_ctx* ctx, const float* d_query, int n_query, const float* d_train,
                              int n_train, int k, int* d_idx, float* d_dist);
 
+/* ---- matching a whole batch (segments given by device-resident offsets) ----- */
+/* knnMatch (src/main.cpp:25-27) for every image of a batch in one enqueue.
+ * Query rows [q_offsets[b], q_offsets[b+1]) of d_query are segment b,
+ * b < n_segments; d_q_offsets is a device array of n_segments + 1 ints, exactly
+ * what sift_detect_compute_batch writes to d_img_offsets.  The offsets are read
+ * on the device only, and every bound is clamped to q_cap (t_cap), the row
+ * capacity of the buffer, so the batch call's overflow convention (the last
+ * offset holds the true total) never reads or writes past a buffer.
+ * Train side: d_t_offsets == NULL -- every segment searches all t_cap rows of
+ * d_train ("find this object in every frame"); otherwise segment b searches
+ * rows [t_offsets[b], t_offsets[b+1]) ("frame b against frame b+1").  Result
+ * indices are local to the train segment (global when the train set is shared).
+ * Distance, order, tie rule and the -1 / +inf fill are sift_knn_match_l1's.
+ * d_idx / d_dist are [q_cap][k]; rows before q_offsets[0] and rows at or past
+ * min(q_offsets[n_segments], q_cap) are left untouched.
+ * Consecutive frames of one batch need no host value: d_train = d_query,
+ * d_t_offsets = d_q_offsets + 1, t_cap = q_cap, n_segments = batch - 1.
+ * Enqueued on the context stream, no synchronisation (the scratch grows, with
+ * a wait, only when a call needs more than any call before it).  n_segments
+ * == 0 or q_cap == 0: SIFT_OK, nothing enqueued. */
+int sift_knn_match_l1_segmented_device(sift_ctx* ctx, const float* d_query, const int* d_q_offsets,
+                                       int n_segments, int q_cap, const float* d_train,
+                                       const int* d_t_offsets /* NULL = shared */, int t_cap, int k, int* d_idx,
+                                       float* d_dist);
+/* Host buffers (synchronous); query has q_cap rows, train t_cap rows: */
+int sift_knn_match_l1_segmented(sift_ctx* ctx, const float* query, const int* q_offsets, int n_segments,
+                                int q_cap, const float* train, const int* t_offsets /* NULL = shared */,
+                                int t_cap, int k, int* idx, float* dist);
+
+/* One kept match: cv::DMatch's queryIdx / trainIdx (local to their segments),
+ * distance, and the segment in imgIdx's place.  16 bytes. */
+typedef struct sift_match {
+  int32_t query, train;
+  float distance;
+  int32_t segment;
+} sift_match;
+
+/* The ratio test and the point gather of the application (src/main.cpp:28-52)
+ * on the k = 2 output of the segmented matcher, same offsets: query row i is
+ * kept iff idx[i][1] >= 0 and (double)dist[i][0] <= ratio * (double)dist[i][1]
+ * (:36-38).  Kept matches are written densely in query order within a segment
+ * and in segment order overall (an ordered scan, no atomics), so segment b's
+ * records are [m_offsets[b], m_offsets[b+1]); d_m_offsets is n_segments + 1 ints
+ * and its last entry is the true total.  Only the first m_cap records are
+ * written (m_cap = q_cap always suffices).  With d_q_kpts != NULL the point
+ * pairs of :47-52 are gathered as interleaved (x, y) floats, the input of
+ * sift_find_homography: src = the query keypoint (keypoints1[queryIdx].pt),
+ * dst = the train keypoint (keypoints0[trainIdx].pt; d_t_kpts row
+ * t_offsets[segment] + train, or train when d_t_offsets is NULL).  With
+ * d_q_kpts == NULL d_t_kpts, d_src_xy and d_dst_xy are not used.
+ * Enqueued on the context stream, no synchronisation. */
+int sift_ratio_matches_device(sift_ctx* ctx, const int* d_idx, const float* d_dist, const int* d_q_offsets,
+                              int n_segments, int q_cap, double ratio, const sift_keypoint* d_q_kpts /* may be NULL */,
+                              const sift_keypoint* d_t_kpts, const int* d_t_offsets, sift_match* d_matches,
+                              float* d_src_xy, float* d_dst_xy, int m_cap, int* d_m_offsets);
+/* Host buffers (synchronous); q_kpts has q_cap rows and t_kpts t_cap rows
+ * (t_cap is not used when q_kpts is NULL): */
+int sift_ratio_matches(sift_ctx* ctx, const int* idx, const float* dist, const int* q_offsets, int n_segments,
+                       int q_cap, double ratio, const sift_keypoint* q_kpts /* may be NULL */,
+                       const sift_keypoint* t_kpts, int t_cap, const int* t_offsets, sift_match* matches,
+                       float* src_xy, float* dst_xy, int m_cap, int* m_offsets);
+
 /* ---- homography ---------------------------------------- */
 /* Replaces `findHomography(obj, scene, RANSAC)` and `perspectiveTransform`
  * (src/main.cpp:54-62): n point pairs as interleaved (x, y) floats, OpenCV's

@@ -98,9 +98,11 @@ struct StageRec {
 
 const char* const kStageNames[] = {"blur_base", "blur_octave", "decimate", "dog", "extrema",
                                    "refine_orient", "emit", "descriptor", "upload", "download",
-                                   "blur_1d", "pyramid_fast", "match", "blur_octave_sym"};
+                                   "blur_1d", "pyramid_fast", "match", "blur_octave_sym", "match_segmented",
+                                   "ratio_matches"};
 enum Stage { ST_BLUR_BASE, ST_BLUR_OCT, ST_DECIMATE, ST_DOG, ST_EXTREMA, ST_REFINE, ST_EMIT,
-             ST_DESC, ST_UPLOAD, ST_DOWNLOAD, ST_BLUR1D, ST_PYR_FAST, ST_MATCH, ST_BLUR_SYM, ST_N };
+             ST_DESC, ST_UPLOAD, ST_DOWNLOAD, ST_BLUR1D, ST_PYR_FAST, ST_MATCH, ST_BLUR_SYM, ST_MATCH_SEG,
+             ST_RATIO, ST_N };
 
 template <typename T>
 hipError_t dmalloc(T** p, size_t count) {
@@ -1295,6 +1297,198 @@ int sift_knn_match_l1(sift_ctx* c, const float* query, int n_query, const float*
   HIP_TRY(c, hipMemcpyAsync(idx, di, (size_t)n_query * k * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(dist, dd, (size_t)n_query * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SIFT_OK;
+}
+
+// ---- a whole batch: segmented knnMatch, ratio test, point pairs (src/main.cpp:25-52) ----
+namespace {
+
+int check_seg_args(sift_ctx* c, int n_segments, int q_cap, int t_cap) {
+  if (n_segments < 0 || q_cap < 0 || t_cap < 0) return fail(c, SIFT_E_INVALID, "negative count");
+  return SIFT_OK;
+}
+
+// Scratch of one segmented call, sized from the capacities alone: tile table, then the partials.
+struct SegScratch {
+  int splits;
+  size_t tile_b, pd_b, pi_b;
+  size_t bytes() const { return tile_b + pd_b + pi_b; }
+};
+
+SegScratch seg_scratch(int q_cap, int n_segments, int t_cap, bool seg_train) {
+  SegScratch s;
+  s.splits = knn_seg_splits(q_cap, n_segments, t_cap, seg_train);
+  const size_t part = s.splits > 1 ? (size_t)s.splits * q_cap : 0;
+  s.tile_b = align256((size_t)(n_segments + 1) * sizeof(int));
+  s.pd_b = align256(part * sizeof(float2));
+  s.pi_b = align256(part * sizeof(int2));
+  return s;
+}
+
+// Scratch at d_match + off (already ensured).
+int knn_seg_device(sift_ctx* c, const float* q, const int* qoff, int n_segments, int q_cap, const float* t,
+                   const int* toff, int t_cap, int k, int* idx, float* dist, size_t off) {
+  const SegScratch s = seg_scratch(q_cap, n_segments, t_cap, toff != nullptr);
+  char* base = static_cast<char*>(c->d_match) + off;
+  {
+    StageScope sc(c, ST_MATCH_SEG);  // the work depends on offsets only the device knows
+    launch_knn_l1_seg(c->stream, q, qoff, n_segments, q_cap, t, toff, t_cap, k, s.splits,
+                      reinterpret_cast<int*>(base), reinterpret_cast<float2*>(base + s.tile_b),
+                      reinterpret_cast<int2*>(base + s.tile_b + s.pd_b), idx, dist);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
+size_t ratio_scratch_bytes(int q_cap) { return align256((size_t)(ratio_blocks(q_cap) + 1) * sizeof(int)); }
+
+int ratio_device(sift_ctx* c, const int* idx, const float* dist, const int* qoff, int n_segments, int q_cap,
+                 double ratio, const sift_keypoint* q_kpts, const sift_keypoint* t_kpts, const int* toff,
+                 sift_match* matches, float* src_xy, float* dst_xy, int m_cap, int* moff, size_t off) {
+  {
+    StageScope sc(c, ST_RATIO, 0, 16.0 * q_cap);
+    launch_ratio_matches(c->stream, idx, dist, qoff, n_segments, q_cap, ratio, q_kpts, t_kpts, toff, matches,
+                         src_xy, dst_xy, m_cap, moff, reinterpret_cast<int*>(static_cast<char*>(c->d_match) + off));
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
+int clamp_off(int v, int cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
+
+}  // namespace
+
+int sift_knn_match_l1_segmented_device(sift_ctx* c, const float* d_query, const int* d_q_offsets, int n_segments,
+                                       int q_cap, const float* d_train, const int* d_t_offsets, int t_cap, int k,
+                                       int* d_idx, float* d_dist) {
+  if (!c) return SIFT_E_INVALID;
+  int rc = check_seg_args(c, n_segments, q_cap, t_cap);
+  if (rc) return rc;
+  if (k != 1 && k != 2) return fail(c, SIFT_E_INVALID, "k must be 1 or 2");
+  if (n_segments == 0 || q_cap == 0) return SIFT_OK;
+  if (!d_query || !d_q_offsets || !d_idx || !d_dist || (t_cap > 0 && !d_train))
+    return fail(c, SIFT_E_INVALID, "null buffer");
+  if ((reinterpret_cast<uintptr_t>(d_query) | reinterpret_cast<uintptr_t>(d_train)) & 15)
+    return fail(c, SIFT_E_INVALID, "descriptor rows must be 16-byte aligned");
+  (void)hipSetDevice(c->device);
+  if ((rc = ensure_match(c, seg_scratch(q_cap, n_segments, t_cap, d_t_offsets != nullptr).bytes()))) return rc;
+  return knn_seg_device(c, d_query, d_q_offsets, n_segments, q_cap, d_train, d_t_offsets, t_cap, k, d_idx, d_dist,
+                        0);
+}
+
+int sift_knn_match_l1_segmented(sift_ctx* c, const float* query, const int* q_offsets, int n_segments, int q_cap,
+                                const float* train, const int* t_offsets, int t_cap, int k, int* idx, float* dist) {
+  if (!c) return SIFT_E_INVALID;
+  int rc = check_seg_args(c, n_segments, q_cap, t_cap);
+  if (rc) return rc;
+  if (k != 1 && k != 2) return fail(c, SIFT_E_INVALID, "k must be 1 or 2");
+  if (n_segments == 0 || q_cap == 0) return SIFT_OK;
+  if (!query || !q_offsets || !idx || !dist || (t_cap > 0 && !train)) return fail(c, SIFT_E_INVALID, "null buffer");
+  (void)hipSetDevice(c->device);
+  const size_t row = kDescLen * sizeof(float), ob = (size_t)(n_segments + 1) * sizeof(int);
+  const size_t qb = align256((size_t)q_cap * row), tb = align256((size_t)(t_cap ? t_cap : 1) * row);
+  const size_t ib = align256((size_t)q_cap * k * sizeof(int)), db = align256((size_t)q_cap * k * sizeof(float));
+  const size_t fb = align256(ob);
+  const size_t off = qb + tb + ib + db + 2 * fb;
+  if ((rc = ensure_match(c, off + seg_scratch(q_cap, n_segments, t_cap, t_offsets != nullptr).bytes()))) return rc;
+  char* base = static_cast<char*>(c->d_match);
+  float* dq = reinterpret_cast<float*>(base);
+  float* dt = reinterpret_cast<float*>(base + qb);
+  int* di = reinterpret_cast<int*>(base + qb + tb);
+  float* dd = reinterpret_cast<float*>(base + qb + tb + ib);
+  int* dqo = reinterpret_cast<int*>(base + qb + tb + ib + db);
+  int* dto = t_offsets ? reinterpret_cast<int*>(base + qb + tb + ib + db + fb) : nullptr;
+  HIP_TRY(c, hipMemcpyAsync(dq, query, (size_t)q_cap * row, hipMemcpyHostToDevice, c->stream));
+  if (t_cap) HIP_TRY(c, hipMemcpyAsync(dt, train, (size_t)t_cap * row, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(dqo, q_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  if (dto) HIP_TRY(c, hipMemcpyAsync(dto, t_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  if ((rc = knn_seg_device(c, dq, dqo, n_segments, q_cap, dt, dto, t_cap, k, di, dd, off))) return rc;
+  // only the live rows come back: the others are left untouched, as in the device form
+  const int lo = clamp_off(q_offsets[0], q_cap), hi = clamp_off(q_offsets[n_segments], q_cap);
+  if (hi > lo) {
+    const size_t n = (size_t)(hi - lo) * k, o = (size_t)lo * k;
+    HIP_TRY(c, hipMemcpyAsync(idx + o, di + o, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dist + o, dd + o, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SIFT_OK;
+}
+
+int sift_ratio_matches_device(sift_ctx* c, const int* d_idx, const float* d_dist, const int* d_q_offsets,
+                              int n_segments, int q_cap, double ratio, const sift_keypoint* d_q_kpts,
+                              const sift_keypoint* d_t_kpts, const int* d_t_offsets, sift_match* d_matches,
+                              float* d_src_xy, float* d_dst_xy, int m_cap, int* d_m_offsets) {
+  if (!c) return SIFT_E_INVALID;
+  int rc = check_seg_args(c, n_segments, q_cap, m_cap);
+  if (rc) return rc;
+  if (n_segments == 0 || q_cap == 0) return SIFT_OK;
+  if (!d_idx || !d_dist || !d_q_offsets || !d_m_offsets || (m_cap > 0 && !d_matches))
+    return fail(c, SIFT_E_INVALID, "null buffer");
+  if (d_q_kpts && (!d_t_kpts || (m_cap > 0 && (!d_src_xy || !d_dst_xy))))
+    return fail(c, SIFT_E_INVALID, "point pairs need the train keypoints and both xy buffers");
+  (void)hipSetDevice(c->device);
+  if ((rc = ensure_match(c, ratio_scratch_bytes(q_cap)))) return rc;
+  return ratio_device(c, d_idx, d_dist, d_q_offsets, n_segments, q_cap, ratio, d_q_kpts, d_t_kpts, d_t_offsets,
+                      d_matches, d_src_xy, d_dst_xy, m_cap, d_m_offsets, 0);
+}
+
+int sift_ratio_matches(sift_ctx* c, const int* idx, const float* dist, const int* q_offsets, int n_segments,
+                       int q_cap, double ratio, const sift_keypoint* q_kpts, const sift_keypoint* t_kpts, int t_cap,
+                       const int* t_offsets, sift_match* matches, float* src_xy, float* dst_xy, int m_cap,
+                       int* m_offsets) {
+  if (!c) return SIFT_E_INVALID;
+  int rc = check_seg_args(c, n_segments, q_cap, m_cap);
+  if (rc) return rc;
+  if (q_kpts && t_cap < 0) return fail(c, SIFT_E_INVALID, "negative count");
+  if (n_segments == 0 || q_cap == 0) return SIFT_OK;
+  if (!idx || !dist || !q_offsets || !m_offsets || (m_cap > 0 && !matches))
+    return fail(c, SIFT_E_INVALID, "null buffer");
+  if (q_kpts && (!t_kpts || (m_cap > 0 && (!src_xy || !dst_xy))))
+    return fail(c, SIFT_E_INVALID, "point pairs need the train keypoints and both xy buffers");
+  (void)hipSetDevice(c->device);
+  const size_t ob = (size_t)(n_segments + 1) * sizeof(int), fb = align256(ob);
+  const size_t ib = align256((size_t)q_cap * 2 * sizeof(int)), db = align256((size_t)q_cap * 2 * sizeof(float));
+  const size_t qk = q_kpts ? align256((size_t)q_cap * sizeof(sift_keypoint)) : 0;
+  const size_t tk = q_kpts ? align256((size_t)(t_cap ? t_cap : 1) * sizeof(sift_keypoint)) : 0;
+  const size_t mb = align256((size_t)(m_cap ? m_cap : 1) * sizeof(sift_match));
+  const size_t xb = q_kpts ? align256((size_t)(m_cap ? m_cap : 1) * 2 * sizeof(float)) : 0;
+  const size_t off = ib + db + 3 * fb + qk + tk + mb + 2 * xb;
+  if ((rc = ensure_match(c, off + ratio_scratch_bytes(q_cap)))) return rc;
+  char* p = static_cast<char*>(c->d_match);
+  int* di = reinterpret_cast<int*>(p);                       p += ib;
+  float* dd = reinterpret_cast<float*>(p);                   p += db;
+  int* dqo = reinterpret_cast<int*>(p);                      p += fb;
+  int* dto = t_offsets ? reinterpret_cast<int*>(p) : nullptr; p += fb;
+  int* dmo = reinterpret_cast<int*>(p);                      p += fb;
+  sift_keypoint* dqk = q_kpts ? reinterpret_cast<sift_keypoint*>(p) : nullptr; p += qk;
+  sift_keypoint* dtk = q_kpts ? reinterpret_cast<sift_keypoint*>(p) : nullptr; p += tk;
+  sift_match* dm = reinterpret_cast<sift_match*>(p);         p += mb;
+  float* dsx = q_kpts ? reinterpret_cast<float*>(p) : nullptr; p += xb;
+  float* ddx = q_kpts ? reinterpret_cast<float*>(p) : nullptr;
+  HIP_TRY(c, hipMemcpyAsync(di, idx, (size_t)q_cap * 2 * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(dd, dist, (size_t)q_cap * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(dqo, q_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  if (dto) HIP_TRY(c, hipMemcpyAsync(dto, t_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  if (q_kpts) {
+    HIP_TRY(c, hipMemcpyAsync(dqk, q_kpts, (size_t)q_cap * sizeof(sift_keypoint), hipMemcpyHostToDevice, c->stream));
+    if (t_cap)
+      HIP_TRY(c, hipMemcpyAsync(dtk, t_kpts, (size_t)t_cap * sizeof(sift_keypoint), hipMemcpyHostToDevice,
+                                c->stream));
+  }
+  if ((rc = ratio_device(c, di, dd, dqo, n_segments, q_cap, ratio, dqk, dtk, dto, dm, dsx, ddx, m_cap, dmo, off)))
+    return rc;
+  HIP_TRY(c, hipMemcpyAsync(m_offsets, dmo, ob, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // only the written records come back
+  const size_t n = (size_t)(m_offsets[n_segments] < m_cap ? m_offsets[n_segments] : m_cap);
+  if (n) {
+    HIP_TRY(c, hipMemcpyAsync(matches, dm, n * sizeof(sift_match), hipMemcpyDeviceToHost, c->stream));
+    if (q_kpts) {
+      HIP_TRY(c, hipMemcpyAsync(src_xy, dsx, n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(dst_xy, ddx, n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
   return SIFT_OK;
 }
 

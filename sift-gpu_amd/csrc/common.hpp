@@ -267,6 +267,22 @@ void perspective_transform(const double* H, const float* xy, int n, float* out);
 int knn_splits(int nq, int nt);
 void launch_knn_l1(hipStream_t st, const float* q, int nq, const float* t, int nt, int k, int splits,
                    float2* part_d, int2* part_i, int* idx, float* dist);
+// Segmented form (device-resident offsets, match.hip): the grid is sized from
+// the capacities, knn_seg_max_tiles() query tiles by knn_seg_splits() train
+// splits; tile_start is [n_segments + 1] ints of scratch, the partials
+// [splits * q_cap] (unused when splits == 1).
+int knn_seg_max_tiles(int q_cap, int n_segments);
+int knn_seg_splits(int q_cap, int n_segments, int t_cap, bool seg_train);
+void launch_knn_l1_seg(hipStream_t st, const float* q, const int* qoff, int n_segments, int q_cap, const float* t,
+                       const int* toff, int t_cap, int k, int splits, int* tile_start, float2* part_d, int2* part_i,
+                       int* idx, float* dist);
+// Ratio test + ordered compaction + point gather; blk_scan is
+// [ratio_blocks(q_cap) + 1] ints of scratch.
+int ratio_blocks(int q_cap);
+void launch_ratio_matches(hipStream_t st, const int* idx, const float* dist, const int* qoff, int n_segments,
+                          int q_cap, double ratio, const sift_keypoint* q_kpts, const sift_keypoint* t_kpts,
+                          const int* toff, sift_match* matches, float* src_xy, float* dst_xy, int m_cap, int* moff,
+                          int* blk_scan);
 // pyramid_pc.hip (SIFT_FLAG_FAST): octave o's five planes by the separable
 // form, plus octave o+1's plane 0 when pyramid_fuses_decimation(L, o + 1)
 // (else decimate first), from a producer wave and three consumer waves

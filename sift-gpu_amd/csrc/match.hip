@@ -22,6 +22,10 @@
 // pair (v_sub, v_add with |x|), 256 per (query, train) pair; the LDS reads are
 // 512 B per row per wave.  The 4 waves' top-2 lists merge in LDS; splits merge
 // in knn_merge_kernel.
+//
+// A whole batch (segments given by device-resident offsets): the same tile in
+// knn_l1_seg_kernel, then the ratio test with ordered compaction and the point
+// gather of src/main.cpp:28-52 (ratio_*_kernel); DESIGN.md §6a.
 #include "common.hpp"
 
 #include <float.h>
@@ -54,6 +58,29 @@ __device__ __forceinline__ void insert(Best2& b, float d, int i) {
   }
 }
 
+// normL1_ of one query (registers) against one staged train row (LDS, the same
+// row for every lane): the summation order of the file comment.
+__device__ __forceinline__ float l1_row(const float4* tr, const float4 (&qv)[kV4]) {
+  float p[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) p[k] = 0.f;
+#pragma unroll
+  for (int g = 0; g < kDescLen / 8; ++g) {
+    const float4 a = tr[2 * g], b = tr[2 * g + 1];
+    const float4 x = qv[2 * g], y = qv[2 * g + 1];
+    p[0] = p[0] + fabsf(x.x - a.x);
+    p[1] = p[1] + fabsf(x.y - a.y);
+    p[2] = p[2] + fabsf(x.z - a.z);
+    p[3] = p[3] + fabsf(x.w - a.w);
+    p[4] = p[4] + fabsf(y.x - b.x);
+    p[5] = p[5] + fabsf(y.y - b.y);
+    p[6] = p[6] + fabsf(y.z - b.z);
+    p[7] = p[7] + fabsf(y.w - b.w);
+  }
+  const float q0 = p[0] + p[4], q1 = p[1] + p[5], q2 = p[2] + p[6], q3 = p[3] + p[7];
+  return (q0 + q1) + (q2 + q3);
+}
+
 __global__ __launch_bounds__(256) void knn_l1_kernel(const float* __restrict__ q, int nq, const float* __restrict__ t,
                                                      int nt, int per_split, float2* __restrict__ part_d,
                                                      int2* __restrict__ part_i) {
@@ -77,25 +104,7 @@ __global__ __launch_bounds__(256) void knn_l1_kernel(const float* __restrict__ q
     for (int u = threadIdx.x; u < nrow * kV4; u += 256) tl[u] = src[u];
     __syncthreads();
     for (int r = wv; r < nrow; r += 4) {
-      const float4* tr = tl + r * kV4;
-      float p[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) p[k] = 0.f;
-#pragma unroll
-      for (int g = 0; g < kDescLen / 8; ++g) {
-        const float4 a = tr[2 * g], b = tr[2 * g + 1];
-        const float4 x = qv[2 * g], y = qv[2 * g + 1];
-        p[0] = p[0] + fabsf(x.x - a.x);
-        p[1] = p[1] + fabsf(x.y - a.y);
-        p[2] = p[2] + fabsf(x.z - a.z);
-        p[3] = p[3] + fabsf(x.w - a.w);
-        p[4] = p[4] + fabsf(y.x - b.x);
-        p[5] = p[5] + fabsf(y.y - b.y);
-        p[6] = p[6] + fabsf(y.z - b.z);
-        p[7] = p[7] + fabsf(y.w - b.w);
-      }
-      const float q0 = p[0] + p[4], q1 = p[1] + p[5], q2 = p[2] + p[6], q3 = p[3] + p[7];
-      insert(best, (q0 + q1) + (q2 + q3), c0 + r);
+      insert(best, l1_row(tl + r * kV4, qv), c0 + r);
     }
   }
   md[wv][0][lane] = best.d1;
@@ -135,6 +144,270 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const float2* __restrict
   }
 }
 
+// ---- segmented form: a whole batch in one launch sequence ---------------------
+// Query rows [qoff[b], qoff[b+1]) are segment b; the offsets live on the device
+// (sift_detect_compute_batch's d_img_offsets) and are never read by the host.
+// Every bound is clamped to the buffer's row capacity, because the batch call
+// leaves the true total in the last offset even when it exceeds kp_cap.
+__device__ __forceinline__ int clamp_row(int v, int cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
+
+// Largest b in [0, n) with clamp(off[b]) <= x; the caller guarantees
+// clamp(off[0]) <= x < clamp(off[n]).  Empty segments (equal offsets) are
+// skipped: the result's next offset is above x.
+__device__ __forceinline__ int seg_of(const int* __restrict__ off, int n, int cap, int x) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (clamp_row(off[mid], cap) <= x) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// Prologue (one workgroup): tile_start[b] = number of 64-query tiles of the
+// segments before b, tile_start[nseg] = all tiles.  A tile never spans two
+// segments, so with segmented train it has one train range.
+__global__ __launch_bounds__(256) void seg_tiles_kernel(const int* __restrict__ qoff, int nseg, int q_cap,
+                                                        int* __restrict__ tile_start) {
+  __shared__ int wsum[4];
+  __shared__ int carry_s;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (threadIdx.x == 0) carry_s = 0;
+  __syncthreads();
+  for (int b0 = 0; b0 < nseg; b0 += 256) {
+    const int b = b0 + threadIdx.x;
+    int n = 0;
+    if (b < nseg) {
+      const int s = clamp_row(qoff[b], q_cap), e = clamp_row(qoff[b + 1], q_cap);
+      n = e > s ? (e - s + kQT - 1) / kQT : 0;
+    }
+    int v = n;  // inclusive scan over the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int u = __shfl_up(v, d);
+      if (lane >= d) v += u;
+    }
+    if (lane == 63) wsum[wv] = v;
+    __syncthreads();
+    int base = carry_s;
+    for (int w = 0; w < wv; ++w) base += wsum[w];
+    if (b < nseg) tile_start[b] = base + v - n;
+    __syncthreads();
+    if (threadIdx.x == 255) carry_s = base + v;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) tile_start[nseg] = carry_s;
+}
+
+// knn_l1_kernel's tile (64 queries in VGPRs, 64-row train chunks in LDS,
+// broadcast reads) with the bounds taken from the device: grid.x covers the
+// most tiles the capacities allow, workgroups past tile_start[nseg] exit.
+// grid.y splits every segment's own train range evenly.  Indices are local to
+// the train range.  splits == 1 writes idx/dist directly.
+__global__ __launch_bounds__(256) void knn_l1_seg_kernel(const float* __restrict__ q, const int* __restrict__ qoff,
+                                                         int nseg, int q_cap, const float* __restrict__ t,
+                                                         const int* __restrict__ toff, int t_cap,
+                                                         const int* __restrict__ tile_start, int splits, int k,
+                                                         float2* __restrict__ part_d, int2* __restrict__ part_i,
+                                                         int* __restrict__ idx, float* __restrict__ dist) {
+  __shared__ float4 tl[kTC * kV4];  // 32 KB
+  __shared__ float md[4][2][kQT];
+  __shared__ int mi[4][2][kQT];
+  const int tile = blockIdx.x;
+  if (tile >= tile_start[nseg]) return;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int b = seg_of(tile_start, nseg, 0x7fffffff, tile);
+  const int qe = clamp_row(qoff[b + 1], q_cap);
+  const int qi = clamp_row(qoff[b], q_cap) + (tile - tile_start[b]) * kQT + lane;  // < qe for lane 0
+  int ts = 0, te = t_cap;
+  if (toff) {
+    ts = clamp_row(toff[b], t_cap);
+    te = clamp_row(toff[b + 1], t_cap);
+    te = te < ts ? ts : te;
+  }
+  const int per = (((te - ts) + splits - 1) / splits + kTC - 1) / kTC * kTC;
+  const long long t0l = ts + (long long)blockIdx.y * per;
+  const int t0 = t0l < te ? (int)t0l : te, t1 = (te - t0) < per ? te : t0 + per;
+  float4 qv[kV4];
+  {
+    const float4* qp = reinterpret_cast<const float4*>(q + (long long)min(qi, qe - 1) * kDescLen);
+#pragma unroll
+    for (int v = 0; v < kV4; ++v) qv[v] = qp[v];
+  }
+  Best2 best{INFINITY, INFINITY, -1, -1};
+  for (int c0 = t0; c0 < t1; c0 += kTC) {
+    const int nrow = min(kTC, t1 - c0);
+    __syncthreads();
+    const float4* src = reinterpret_cast<const float4*>(t + (long long)c0 * kDescLen);
+    for (int u = threadIdx.x; u < nrow * kV4; u += 256) tl[u] = src[u];
+    __syncthreads();
+    for (int r = wv; r < nrow; r += 4) insert(best, l1_row(tl + r * kV4, qv), c0 + r - ts);
+  }
+  md[wv][0][lane] = best.d1;
+  md[wv][1][lane] = best.d2;
+  mi[wv][0][lane] = best.i1;
+  mi[wv][1][lane] = best.i2;
+  __syncthreads();
+  if (wv == 0 && qi < qe) {
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+      insert(best, md[w][0][lane], mi[w][0][lane]);
+      insert(best, md[w][1][lane], mi[w][1][lane]);
+    }
+    if (splits == 1) {
+      idx[(long long)qi * k] = best.i1;
+      dist[(long long)qi * k] = best.d1;
+      if (k == 2) {
+        idx[(long long)qi * k + 1] = best.i2;
+        dist[(long long)qi * k + 1] = best.d2;
+      }
+    } else {
+      const long long o = (long long)blockIdx.y * q_cap + qi;
+      part_d[o] = make_float2(best.d1, best.d2);
+      part_i[o] = make_int2(best.i1, best.i2);
+    }
+  }
+}
+
+// knn_merge_kernel over the live rows [clamp(qoff[0]), clamp(qoff[nseg])) only.
+__global__ __launch_bounds__(256) void knn_seg_merge_kernel(const float2* __restrict__ part_d,
+                                                            const int2* __restrict__ part_i,
+                                                            const int* __restrict__ qoff, int nseg, int q_cap,
+                                                            int splits, int k, int* __restrict__ idx,
+                                                            float* __restrict__ dist) {
+  const int qi = blockIdx.x * 256 + threadIdx.x;
+  if (qi < clamp_row(qoff[0], q_cap) || qi >= clamp_row(qoff[nseg], q_cap)) return;
+  Best2 best{INFINITY, INFINITY, -1, -1};
+  for (int s = 0; s < splits; ++s) {
+    const float2 d = part_d[(long long)s * q_cap + qi];
+    const int2 i = part_i[(long long)s * q_cap + qi];
+    insert(best, d.x, i.x);
+    insert(best, d.y, i.y);
+  }
+  idx[(long long)qi * k] = best.i1;
+  dist[(long long)qi * k] = best.d1;
+  if (k == 2) {
+    idx[(long long)qi * k + 1] = best.i2;
+    dist[(long long)qi * k + 1] = best.d2;
+  }
+}
+
+// ---- ratio test, ordered compaction, point gather (src/main.cpp:28-52) ---------
+// Three launches, like the detect stage's scan: kept rows per 256-row block, an
+// exclusive scan of the block counts in one workgroup, and the emit, which
+// recomputes the flags and ranks them inside the block.  The order is the row
+// order; no atomic takes part.
+constexpr int kRB = 256;  // rows per block of the ratio stage
+
+struct RatioIn {
+  const int* idx;     // [q_cap][2]
+  const float* dist;  // [q_cap][2]
+  const int* qoff;
+  int nseg, q_cap;
+  double ratio;
+};
+
+// m1.distance <= ratio * m2.distance in double (src/main.cpp:38); a row without
+// a second neighbour is skipped (:36).  Rows outside the live range are never kept.
+__device__ __forceinline__ bool ratio_keep(const RatioIn& R, int i, int lo, int hi) {
+  if (i < lo || i >= hi) return false;
+  if (R.idx[2ll * i + 1] < 0) return false;
+  return (double)R.dist[2ll * i] <= R.ratio * (double)R.dist[2ll * i + 1];
+}
+
+__global__ __launch_bounds__(kRB) void ratio_count_kernel(RatioIn R, int* __restrict__ blk_cnt) {
+  __shared__ int wcnt[4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int lo = clamp_row(R.qoff[0], R.q_cap), hi = clamp_row(R.qoff[R.nseg], R.q_cap);
+  const bool keep = ratio_keep(R, blockIdx.x * kRB + threadIdx.x, lo, hi);
+  const unsigned long long m = __ballot(keep);
+  if (lane == 0) wcnt[wv] = __popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
+}
+
+// in-place exclusive scan of v[0..n), v[n] = total (one workgroup)
+__global__ __launch_bounds__(1024) void ratio_scan_kernel(int* __restrict__ v, int n) {
+  __shared__ int wsum[16];
+  __shared__ int carry_s;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (threadIdx.x == 0) carry_s = 0;
+  __syncthreads();
+  for (int i0 = 0; i0 < n; i0 += 1024) {
+    const int i = i0 + threadIdx.x;
+    const int x = i < n ? v[i] : 0;
+    int s = x;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int u = __shfl_up(s, d);
+      if (lane >= d) s += u;
+    }
+    if (lane == 63) wsum[wv] = s;
+    __syncthreads();
+    int base = carry_s;
+    for (int w = 0; w < wv; ++w) base += wsum[w];
+    if (i < n) v[i] = base + s - x;
+    __syncthreads();
+    if (threadIdx.x == 1023) carry_s = base + s;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) v[n] = carry_s;
+}
+
+struct RatioOut {
+  const sift_keypoint* q_kpts;  // nullptr: no point pairs
+  const sift_keypoint* t_kpts;
+  const int* toff;              // nullptr: shared train
+  sift_match* matches;
+  float* src_xy;
+  float* dst_xy;
+  int m_cap;
+  int* moff;
+};
+
+// Blocks [0, nblk): one row per thread.  Blocks past nblk: one wave per segment
+// boundary b computes moff[b] = kept rows below clamp(qoff[b]).
+__global__ __launch_bounds__(kRB) void ratio_emit_kernel(RatioIn R, const int* __restrict__ blk_pre, int nblk,
+                                                         RatioOut O) {
+  __shared__ int wcnt[4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int lo = clamp_row(R.qoff[0], R.q_cap), hi = clamp_row(R.qoff[R.nseg], R.q_cap);
+  if ((int)blockIdx.x >= nblk) {
+    const int b = ((int)blockIdx.x - nblk) * 4 + wv;
+    if (b > R.nseg) return;
+    const int r = clamp_row(R.qoff[b], R.q_cap), blk = r / kRB;  // blk == nblk only with no rows to count
+    int cnt = 0;
+    for (int j = blk * kRB + lane; j < r; j += 64) cnt += ratio_keep(R, j, lo, hi) ? 1 : 0;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
+    if (lane == 0) O.moff[b] = blk_pre[blk] + cnt;
+    return;
+  }
+  const int i = blockIdx.x * kRB + threadIdx.x;
+  const bool keep = ratio_keep(R, i, lo, hi);
+  const unsigned long long m = __ballot(keep);
+  if (lane == 0) wcnt[wv] = __popcll(m);
+  __syncthreads();
+  if (!keep) return;
+  int pos = blk_pre[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
+  for (int w = 0; w < wv; ++w) pos += wcnt[w];
+  if (pos >= O.m_cap) return;
+  const int b = seg_of(R.qoff, R.nseg, R.q_cap, i);
+  const int tr = R.idx[2ll * i];
+  sift_match rec;
+  rec.query = i - clamp_row(R.qoff[b], R.q_cap);
+  rec.train = tr;
+  rec.distance = R.dist[2ll * i];
+  rec.segment = b;
+  O.matches[pos] = rec;
+  if (O.q_kpts) {
+    const long long tg = (O.toff ? (long long)O.toff[b] : 0ll) + tr;
+    O.src_xy[2ll * pos] = O.q_kpts[i].x;
+    O.src_xy[2ll * pos + 1] = O.q_kpts[i].y;
+    O.dst_xy[2ll * pos] = O.t_kpts[tg].x;
+    O.dst_xy[2ll * pos + 1] = O.t_kpts[tg].y;
+  }
+}
+
 }  // namespace
 
 int knn_splits(int nq, int nt) {
@@ -153,6 +426,45 @@ void launch_knn_l1(hipStream_t st, const float* q, int nq, const float* t, int n
   hipLaunchKernelGGL(knn_l1_kernel, grid, dim3(256), 0, st, q, nq, t, nt, per, part_d, part_i);
   hipLaunchKernelGGL(knn_merge_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, part_d, part_i, nq, splits, k,
                      idx, dist);
+}
+
+int knn_seg_max_tiles(int q_cap, int n_segments) { return q_cap / kQT + n_segments; }
+
+int knn_seg_splits(int q_cap, int n_segments, int t_cap, bool seg_train) {
+  const int gx = knn_seg_max_tiles(q_cap, n_segments);
+  int s = (2048 + gx - 1) / gx;
+  // segmented train: an even share of the buffer stands in for the segment size
+  const int nt = seg_train ? (t_cap + n_segments - 1) / n_segments : t_cap;
+  const int max_s = (nt + kTC - 1) / kTC;
+  s = s < max_s ? s : max_s;
+  return s < 1 ? 1 : s;
+}
+
+void launch_knn_l1_seg(hipStream_t st, const float* q, const int* qoff, int n_segments, int q_cap, const float* t,
+                       const int* toff, int t_cap, int k, int splits, int* tile_start, float2* part_d, int2* part_i,
+                       int* idx, float* dist) {
+  hipLaunchKernelGGL(seg_tiles_kernel, dim3(1), dim3(256), 0, st, qoff, n_segments, q_cap, tile_start);
+  dim3 grid(knn_seg_max_tiles(q_cap, n_segments), splits);
+  hipLaunchKernelGGL(knn_l1_seg_kernel, grid, dim3(256), 0, st, q, qoff, n_segments, q_cap, t, toff, t_cap,
+                     tile_start, splits, k, part_d, part_i, idx, dist);
+  if (splits > 1)
+    hipLaunchKernelGGL(knn_seg_merge_kernel, dim3((q_cap + 255) / 256), dim3(256), 0, st, part_d, part_i, qoff,
+                       n_segments, q_cap, splits, k, idx, dist);
+}
+
+int ratio_blocks(int q_cap) { return (q_cap + kRB - 1) / kRB; }
+
+void launch_ratio_matches(hipStream_t st, const int* idx, const float* dist, const int* qoff, int n_segments,
+                          int q_cap, double ratio, const sift_keypoint* q_kpts, const sift_keypoint* t_kpts,
+                          const int* toff, sift_match* matches, float* src_xy, float* dst_xy, int m_cap, int* moff,
+                          int* blk_scan) {
+  const int nblk = ratio_blocks(q_cap);
+  const RatioIn R{idx, dist, qoff, n_segments, q_cap, ratio};
+  const RatioOut O{q_kpts, t_kpts, toff, matches, src_xy, dst_xy, m_cap, moff};
+  hipLaunchKernelGGL(ratio_count_kernel, dim3(nblk), dim3(kRB), 0, st, R, blk_scan);
+  hipLaunchKernelGGL(ratio_scan_kernel, dim3(1), dim3(1024), 0, st, blk_scan, nblk);
+  hipLaunchKernelGGL(ratio_emit_kernel, dim3(nblk + (n_segments + 1 + 3) / 4), dim3(kRB), 0, st, R, blk_scan, nblk,
+                     O);
 }
 
 }  // namespace sift

@@ -41,6 +41,9 @@ KEYPOINT_DTYPE = np.dtype(
     [("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
      ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
 assert KEYPOINT_DTYPE.itemsize == 28
+# sift_match: one kept match of ratioMatches (query / train local to their segments)
+MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("distance", "<f4"), ("segment", "<i4")])
+assert MATCH_DTYPE.itemsize == 16
 
 
 class SiftError(RuntimeError):
@@ -108,6 +111,12 @@ def lib():
             "sift_perspective_transform": (ip, [ctypes.POINTER(ctypes.c_double), fp, ip, fp]),
             "sift_bgr8_to_gray_device": (ip, [vp, vp, ip, ip, ip, sz, sz, ip, ip, vp, sz, sz]),
             "sift_knn_match_l1_device": (ip, [vp, vp, ip, vp, ip, ip, vp, vp]),
+            "sift_knn_match_l1_segmented_device": (ip, [vp, vp, vp, ip, ip, vp, vp, ip, ip, vp, vp]),
+            "sift_knn_match_l1_segmented": (ip, [vp, fp, pint, ip, ip, fp, pint, ip, ip, pint, fp]),
+            "sift_ratio_matches_device": (ip, [vp, vp, vp, vp, ip, ip, ctypes.c_double, vp, vp, vp, vp, vp, vp, ip,
+                                               vp]),
+            "sift_ratio_matches": (ip, [vp, pint, fp, pint, ip, ip, ctypes.c_double, vp, vp, ip, pint, vp, fp, fp,
+                                        ip, pint]),
             "sift_multi_shard": (ip, [ip, ip, ip, pint, pint]),
             "sift_multi_merge_offsets": (ip, [ctypes.POINTER(pint), pint, ip, pint]),
             "sift_multi_create": (ip, [pint, ip, ip, ip, ip, ctypes.c_uint, ip, ip, ip, ctypes.POINTER(vp)]),
@@ -339,6 +348,89 @@ class Context:
                     self._L.sift_knn_match_l1_device(self.h, ctypes.c_void_p(query_ptr), n_query,
                                                      ctypes.c_void_p(train_ptr), n_train, k,
                                                      ctypes.c_void_p(idx_ptr), ctypes.c_void_p(dist_ptr)))
+
+    # ---- a whole batch: segmented matcher + ratio test + point pairs -------
+    def knn_match_segmented_device(self, query_ptr: int, q_offsets_ptr: int, n_segments: int, q_cap: int,
+                                   train_ptr: int, t_offsets_ptr: int | None, t_cap: int, k: int, idx_ptr: int,
+                                   dist_ptr: int):
+        """Device-pointer form (no sync): segment b = query rows
+        [q_offsets[b], q_offsets[b+1]), offsets read on the device and clamped to
+        q_cap / t_cap; t_offsets_ptr None = one shared train set.  Consecutive
+        frames of a batch: train_ptr = query_ptr, t_offsets_ptr = q_offsets_ptr + 4,
+        n_segments = batch - 1."""
+        self._check("sift_knn_match_l1_segmented_device",
+                    self._L.sift_knn_match_l1_segmented_device(
+                        self.h, ctypes.c_void_p(query_ptr), ctypes.c_void_p(q_offsets_ptr), n_segments, q_cap,
+                        ctypes.c_void_p(train_ptr), ctypes.c_void_p(t_offsets_ptr or None), t_cap, k,
+                        ctypes.c_void_p(idx_ptr), ctypes.c_void_p(dist_ptr)))
+
+    def ratio_matches_device(self, idx_ptr: int, dist_ptr: int, q_offsets_ptr: int, n_segments: int, q_cap: int,
+                             ratio: float, q_kpts_ptr: int | None, t_kpts_ptr: int | None,
+                             t_offsets_ptr: int | None, matches_ptr: int, src_xy_ptr: int | None,
+                             dst_xy_ptr: int | None, m_cap: int, m_offsets_ptr: int):
+        """Device-pointer form (no sync) of the ratio test, ordered compaction and
+        point gather (src/main.cpp:28-52); q_kpts_ptr None = no point pairs."""
+        vp = lambda p: ctypes.c_void_p(p or None)  # noqa: E731
+        self._check("sift_ratio_matches_device",
+                    self._L.sift_ratio_matches_device(self.h, vp(idx_ptr), vp(dist_ptr), vp(q_offsets_ptr),
+                                                      n_segments, q_cap, float(ratio), vp(q_kpts_ptr),
+                                                      vp(t_kpts_ptr), vp(t_offsets_ptr), vp(matches_ptr),
+                                                      vp(src_xy_ptr), vp(dst_xy_ptr), m_cap, vp(m_offsets_ptr)))
+
+    def knnMatchSegmented(self, query: np.ndarray, q_offsets, train: np.ndarray, t_offsets=None, k: int = 2):
+        """knnMatch for every segment at once (host arrays): idx, dist [len(query), k]
+        with train indices local to the segment's train rows -- all of `train`
+        (t_offsets None) or rows [t_offsets[b], t_offsets[b+1]).  Rows outside
+        [q_offsets[0], q_offsets[-1]) keep idx -1 / dist +inf."""
+        q = np.ascontiguousarray(query, np.float32).reshape(-1, DESC_LEN)
+        t = np.ascontiguousarray(train, np.float32).reshape(-1, DESC_LEN)
+        qo = np.ascontiguousarray(q_offsets, np.int32)
+        to = None if t_offsets is None else np.ascontiguousarray(t_offsets, np.int32)
+        if qo.ndim != 1 or len(qo) < 1 or (to is not None and to.shape != qo.shape):
+            raise ValueError("offsets must be 1-D, n_segments + 1 entries each")
+        pint = ctypes.POINTER(ctypes.c_int)
+        idx = np.full((len(q), k), -1, np.int32)
+        dist = np.full((len(q), k), np.inf, np.float32)
+        self._check("sift_knn_match_l1_segmented",
+                    self._L.sift_knn_match_l1_segmented(
+                        self.h, _fp(q), qo.ctypes.data_as(pint), len(qo) - 1, len(q), _fp(t),
+                        None if to is None else to.ctypes.data_as(pint), len(t), k, idx.ctypes.data_as(pint),
+                        _fp(dist)))
+        return idx, dist
+
+    def ratioMatches(self, idx: np.ndarray, dist: np.ndarray, q_offsets, ratio: float = 0.86, q_kpts=None,
+                     t_kpts=None, t_offsets=None):
+        """Ratio test + ordered compaction (+ point pairs with q_kpts / t_kpts) on
+        knnMatchSegmented's k = 2 output: (matches [MATCH_DTYPE], m_offsets
+        [n_segments + 1], src_xy, dst_xy [n, 2] float32 or None)."""
+        ix = np.ascontiguousarray(idx, np.int32).reshape(-1, 2)
+        ds = np.ascontiguousarray(dist, np.float32).reshape(-1, 2)
+        qo = np.ascontiguousarray(q_offsets, np.int32)
+        to = None if t_offsets is None else np.ascontiguousarray(t_offsets, np.int32)
+        if len(ix) != len(ds) or qo.ndim != 1 or len(qo) < 1 or (to is not None and to.shape != qo.shape):
+            raise ValueError("idx / dist must be [n, 2] and the offsets n_segments + 1 entries each")
+        if (q_kpts is None) != (t_kpts is None):
+            raise ValueError("point pairs need both q_kpts and t_kpts")
+        pint = ctypes.POINTER(ctypes.c_int)
+        n = len(ix)
+        matches = np.zeros(n, MATCH_DTYPE)
+        moff = np.zeros(len(qo), np.int32)
+        qk = tk = src = dst = None
+        if q_kpts is not None:
+            qk = np.ascontiguousarray(q_kpts, KEYPOINT_DTYPE)
+            tk = np.ascontiguousarray(t_kpts, KEYPOINT_DTYPE)
+            if len(qk) != n:
+                raise ValueError("q_kpts must have one row per query row")
+            src, dst = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32)
+        self._check("sift_ratio_matches",
+                    self._L.sift_ratio_matches(
+                        self.h, ix.ctypes.data_as(pint), _fp(ds), qo.ctypes.data_as(pint), len(qo) - 1, n,
+                        float(ratio), None if qk is None else qk.ctypes.data, None if tk is None else tk.ctypes.data,
+                        0 if tk is None else len(tk), None if to is None else to.ctypes.data_as(pint),
+                        matches.ctypes.data, None if src is None else _fp(src), None if dst is None else _fp(dst),
+                        n, moff.ctypes.data_as(pint)))
+        m = int(moff[-1])
+        return matches[:m], moff, (None if src is None else src[:m]), (None if dst is None else dst[:m])
 
     # ---- device batch API ------------------------------------------------
     def synth_images(self, out_ptr: int, batch: int, rows: int, cols: int, row_stride: int,

@@ -50,6 +50,9 @@ def lib():
         L.so_find_scale_space_extrema.restype = ctypes.c_int
         L.so_find_scale_space_extrema.argtypes = [fp, fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                   ctypes.c_void_p, ctypes.c_int]
+        L.so_extrema_stats.restype = ctypes.c_int
+        L.so_extrema_stats.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]
+        L.so_extrema_stats_reset.argtypes = []
         L.so_calc_descriptors.argtypes = [fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_void_p, ctypes.c_int, fp, ctypes.c_int]
         L.so_sift.restype = ctypes.c_int
@@ -164,6 +167,34 @@ def find_scale_space_extrema(gpyr, dog, rows, cols, n_octaves=5) -> np.ndarray:
         if n <= cap:
             return kps[:n].copy()
         cap = n
+
+
+# order of the SO_ST_* counters in sift_oracle.h
+_STAT_SCALARS = ("raw_extrema", "rej_offset_huge", "rej_layer", "rej_border", "rej_max_interp", "rej_contrast",
+                 "rej_det", "rej_edge", "moved_layer", "moved_rc", "positive", "negative", "kept",
+                 "orient_clipped", "max_orient_radius")
+_STAT_PEAKS, _STAT_KP_OCTAVES = 19, 8
+
+
+def extrema_stats() -> dict:
+    """Branch counters of the last find_scale_space_extrema / sift call in this
+    process (so_extrema_stats): the scalar counters by name, "peaks_hist"
+    (kept candidates with 0..18 orientation peaks) and "keypoints" (an
+    [octave < 8, layer 1..2] table of keypoint counts)."""
+    n = lib().so_extrema_stats(None, 0)
+    assert n == len(_STAT_SCALARS) + _STAT_PEAKS + 2 * _STAT_KP_OCTAVES
+    buf = (ctypes.c_longlong * n)()
+    lib().so_extrema_stats(buf, n)
+    v = [int(x) for x in buf]
+    out = dict(zip(_STAT_SCALARS, v))
+    k = len(_STAT_SCALARS)
+    out["peaks_hist"] = v[k:k + _STAT_PEAKS]
+    out["keypoints"] = np.array(v[k + _STAT_PEAKS:], np.int64).reshape(_STAT_KP_OCTAVES, 2)
+    return out
+
+
+def extrema_stats_reset() -> None:
+    lib().so_extrema_stats_reset()
 
 
 def calc_descriptors(gpyr, rows, cols, kps: np.ndarray, n_octaves=5, first_octave=0) -> np.ndarray:

@@ -382,6 +382,18 @@ void so_build_dog_pyramid(const float* gpyr, int rows, int cols, int n_octaves, 
     }
 }
 
+/* ---- branch counters of the extrema stage (test coverage only) ----------
+ * Plain globals: the extrema stage is serial.  Counting changes no result. */
+static long long g_stats[SO_STATS_LEN];
+#define STAT(i) (++g_stats[(i)])
+
+void so_extrema_stats_reset(void) { memset(g_stats, 0, sizeof(g_stats)); }
+
+int so_extrema_stats(long long* out, int n) {
+  for (int i = 0; i < n && i < SO_STATS_LEN; ++i) out[i] = g_stats[i];
+  return SO_STATS_LEN;
+}
+
 /* ---- adjustLocalExtrema (src/sift.cpp:287-388) ------------------------- */
 typedef struct { const float* p[32 * 4]; int rows[32], cols[32]; } plane_set;
 
@@ -397,6 +409,7 @@ static int adjust_local_extrema(const plane_set* dog, so_keypoint* kp, int oct, 
   int layer = *layer_io, r = *r_io, c = *c_io;
   float xi = 0, xr = 0, xc = 0, contr = 0;
   int it = 0;
+  int moved_layer = 0, moved_rc = 0; /* counters only */
   for (; it < MAX_INTERP; ++it) {
     const float* cur = dog->p[oct * 4 + layer];
     const float* lo = dog->p[oct * 4 + layer - 1];
@@ -422,16 +435,27 @@ static int adjust_local_extrema(const plane_set* dog, so_keypoint* kp, int oct, 
     xc = -X[0];
     if (fabsf(xi) < 0.5f && fabsf(xr) < 0.5f && fabsf(xc) < 0.5f) break;
     if (fabsf(xi) > (float)(INT_MAX / 3) || fabsf(xr) > (float)(INT_MAX / 3) ||
-        fabsf(xc) > (float)(INT_MAX / 3))
+        fabsf(xc) > (float)(INT_MAX / 3)) {
+      STAT(SO_ST_REJ_HUGE);
       return 0;
+    }
     c += round_f(xc);
     r += round_f(xr);
     layer += round_f(xi);
+    moved_layer |= round_f(xi) != 0;
+    moved_rc |= round_f(xc) != 0 || round_f(xr) != 0;
     if (layer < 1 || layer > N_LAYERS || c < IMG_BORDER || c >= ncols - IMG_BORDER ||
-        r < IMG_BORDER || r >= nrows - IMG_BORDER)
+        r < IMG_BORDER || r >= nrows - IMG_BORDER) {
+      STAT(layer < 1 || layer > N_LAYERS ? SO_ST_REJ_LAYER : SO_ST_REJ_BORDER);
       return 0;
+    }
   }
-  if (it >= MAX_INTERP) return 0;
+  if (it >= MAX_INTERP) {
+    STAT(SO_ST_REJ_MAXIT);
+    return 0;
+  }
+  if (moved_layer) STAT(SO_ST_MOVED_LAYER);
+  if (moved_rc) STAT(SO_ST_MOVED_RC);
   {
     const float* cur = dog->p[oct * 4 + layer];
     const float* lo = dog->p[oct * 4 + layer - 1];
@@ -444,7 +468,10 @@ static int adjust_local_extrema(const plane_set* dog, so_keypoint* kp, int oct, 
     t += g1 * xr;
     t += g2 * xi;
     contr = AT(cur, r, c) * img_scale + t * 0.5f;
-    if (fabsf(contr) * N_LAYERS < (float)K_CONTRAST) return 0;
+    if (fabsf(contr) * N_LAYERS < (float)K_CONTRAST) {
+      STAT(SO_ST_REJ_CONTRAST);
+      return 0;
+    }
     float v2 = AT(cur, r, c) * 2.f;
     float dxx = (AT(cur, r, c + 1) + AT(cur, r, c - 1) - v2) * second_scale;
     float dyy = (AT(cur, r + 1, c) + AT(cur, r - 1, c) - v2) * second_scale;
@@ -453,7 +480,10 @@ static int adjust_local_extrema(const plane_set* dog, so_keypoint* kp, int oct, 
     float tr = dxx + dyy;
     float det = dxx * dyy - dxy * dxy;
     const float et = (float)K_EDGE;
-    if (det <= 0 || tr * tr * et >= (et + 1) * (et + 1) * det) return 0;
+    if (det <= 0 || tr * tr * et >= (et + 1) * (et + 1) * det) {
+      STAT(det <= 0 ? SO_ST_REJ_DET : SO_ST_REJ_EDGE);
+      return 0;
+    }
   }
   kp->x = (c + xc) * (1 << oct);
   kp->y = (r + xr) * (1 << oct);
@@ -490,6 +520,8 @@ static float orientation_hist(const float* img, int nrows, int ncols, int py, in
       ++k;
     }
   }
+  if (k < len) STAT(SO_ST_CLIPPED);
+  if (radius > g_stats[SO_ST_MAX_RADIUS]) g_stats[SO_ST_MAX_RADIUS] = radius;
   len = k;
   so_exp32f(W, W, len);
   so_fast_atan2(Y, X, O, len);
@@ -550,8 +582,12 @@ static int scan_layer(const plane_set* gp, const plane_set* dog, int o, int laye
         is_ext = 0;
       }
       if (!is_ext) continue;
+      STAT(SO_ST_RAW);
+      STAT(v > 0 ? SO_ST_POS : SO_ST_NEG);
       int r1 = r, c1 = c, ly = layer;
       if (!adjust_local_extrema(dog, &kp, o, &ly, &r1, &c1)) continue;
+      STAT(SO_ST_KEPT);
+      int npk = 0; /* counters only */
       float scl = kp.size * 0.5f / (1 << o);
       const float* g = gp->p[o * N_SCALES + ly];
       float omax = orientation_hist(g, nrows, ncols, r1, c1, round_f(ORI_RADIUS * scl),
@@ -567,8 +603,11 @@ static int scan_layer(const plane_set* gp, const plane_set* dog, int o, int laye
           if (fabsf(kp.angle - 360.f) < FLT_EPSILON) kp.angle = 0.f;
           if (count < cap) kps[count] = kp;
           ++count;
+          ++npk;
         }
       }
+      STAT(SO_ST_PEAKS + npk);
+      if (o < SO_ST_KP_OCTAVES) g_stats[SO_ST_KP + o * N_LAYERS + (ly - 1)] += npk;
     }
   }
   return count;
@@ -586,6 +625,7 @@ int so_find_scale_space_extrema(const float* gpyr, const float* dog, int rows, i
   plane_set gp, dp;
   make_planes(gpyr, rows, cols, n_octaves, N_SCALES, &gp);
   make_planes(dog, rows, cols, n_octaves, 4, &dp);
+  so_extrema_stats_reset(); /* the counters describe the last call */
   int count = 0;
   for (int o = 0; o < n_octaves; ++o)
     for (int i = 1; i <= N_LAYERS; ++i) count = scan_layer(&gp, &dp, o, i, kps, cap, count);

@@ -79,6 +79,35 @@ void so_build_dog_pyramid(const float* gpyr, int rows, int cols, int n_octaves, 
 int so_find_scale_space_extrema(const float* gpyr, const float* dog, int rows, int cols,
                                 int n_octaves, so_keypoint* kps, int cap);
 
+/* Branch counters of the last so_find_scale_space_extrema call (so_sift
+ * included), for tests that must know which paths an input reaches.  Purely
+ * additive: counting changes no result.  The extrema stage is serial, the
+ * counters are plain globals (not thread-safe across concurrent calls). */
+enum {
+  SO_ST_RAW = 0,       /* 26-neighbour extrema above the threshold (scan_layer) */
+  SO_ST_REJ_HUGE,      /* an offset above INT_MAX/3 (src/sift.cpp:335-337)      */
+  SO_ST_REJ_LAYER,     /* moved out of layers 1..nOctaveLayers (:344)           */
+  SO_ST_REJ_BORDER,    /* moved into the image border (:345-347)                */
+  SO_ST_REJ_MAXIT,     /* no convergence in SIFT_MAX_INTERP_STEPS (:351)        */
+  SO_ST_REJ_CONTRAST,  /* |contrast| * nOctaveLayers < 0.04 (:365)              */
+  SO_ST_REJ_DET,       /* det <= 0 (:377)                                       */
+  SO_ST_REJ_EDGE,      /* edge ratio (:377), det > 0                            */
+  SO_ST_MOVED_LAYER,   /* converged after a step that changed the layer         */
+  SO_ST_MOVED_RC,      /* converged after a step that changed r or c            */
+  SO_ST_POS,           /* raw extrema with v > 0                                */
+  SO_ST_NEG,           /* raw extrema with v < 0                                */
+  SO_ST_KEPT,          /* candidates that passed adjustLocalExtrema             */
+  SO_ST_CLIPPED,       /* kept, orientation window clipped by the interior      */
+  SO_ST_MAX_RADIUS,    /* largest orientation radius (a maximum, not a count)   */
+  SO_ST_PEAKS,         /* [19] kept candidates with 0..18 orientation peaks     */
+  SO_ST_KP = SO_ST_PEAKS + 19, /* [8][2] keypoints of octave o (< 8), layer 1..2 */
+  SO_ST_KP_OCTAVES = 8,
+  SO_STATS_LEN = SO_ST_KP + SO_ST_KP_OCTAVES * 2
+};
+/* Copies min(n, SO_STATS_LEN) counters into out; returns SO_STATS_LEN. */
+int so_extrema_stats(long long* out, int n);
+void so_extrema_stats_reset(void);
+
 /* calDescriptor (src/sift.cpp:733-753): n rows of 128 floats. */
 void so_calc_descriptors(const float* gpyr, int rows, int cols, int n_octaves,
                          const so_keypoint* kps, int n, float* desc, int first_octave);

@@ -239,11 +239,21 @@ class Context:
         self._check("sift_set_candidate_capacity", self._L.sift_set_candidate_capacity(self.h, per_image))
 
     # ---- host-memory API (reference names) ------------------------------
-    def SIFT_NCL(self, img: np.ndarray):
-        img = np.ascontiguousarray(img, np.float32)
+    def SIFT_NCL(self, img: np.ndarray, row_stride_bytes: int | None = None):
+        """row_stride_bytes None: img is copied to a contiguous float32 array.
+        A number: img's own memory is passed with that row stride (img must be
+        2-D float32 with unit column stride and rows that many bytes apart;
+        0 is the ABI's default, cols * 4)."""
+        if row_stride_bytes is None:
+            img = np.ascontiguousarray(img, np.float32)
+            row_stride_bytes = img.shape[1] * 4
+        elif (img.dtype != np.float32 or img.ndim != 2 or img.strides[1] != 4
+              or img.strides[0] != (row_stride_bytes or img.shape[1] * 4)):
+            raise ValueError("img must be a 2-D float32 view whose rows are row_stride_bytes apart")
         r, c = img.shape
         n = ctypes.c_int(0)
-        rc = self._L.sift_detect_compute(self.h, _fp(img), r, c, c * 4, None, None, 0, ctypes.byref(n))
+        rc = self._L.sift_detect_compute(self.h, img.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), r, c,
+                                         row_stride_bytes, None, None, 0, ctypes.byref(n))
         if rc not in (SIFT_OK, SIFT_E_CAPACITY):
             self._check("sift_detect_compute", rc)
         kps = np.zeros(n.value, KEYPOINT_DTYPE)

@@ -1,0 +1,5 @@
+/* cvmini: forwards to opencv2/core.hpp, the one real stand-in header. */
+#ifndef CVMINI_OPENCV2_HIGHGUI_HPP_
+#define CVMINI_OPENCV2_HIGHGUI_HPP_
+#include "core.hpp"
+#endif

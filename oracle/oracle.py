@@ -2,11 +2,13 @@
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py, always as the checker -- never by the product
-library.  PARITY UNPINNED (see sift_oracle.h): the reference cannot be built in
-this image and has no golden vectors of its own.
+library.  Pinned to the reference's own source, compiled over stand-in OpenCV
+headers (refsrc.py, tests/test_reference_source.py); see sift_oracle.h for what
+is still unpinned.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import subprocess
@@ -60,6 +62,8 @@ def lib():
                               ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]
         L.so_free.argtypes = [ctypes.c_void_p]
         L.so_set_threads.argtypes = [ctypes.c_int]
+        L.so_set_libm.argtypes = [ctypes.c_int]
+        L.so_get_libm.restype = ctypes.c_int
         L.so_synth_image.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, fp]
         L.so_exp32f.argtypes = [fp, fp, ctypes.c_int]
         L.so_fast_atan2.argtypes = [fp, fp, fp, ctypes.c_int]
@@ -100,6 +104,17 @@ def split_planes(packed: np.ndarray, rows: int, cols: int, n_octaves: int, per: 
 
 def set_threads(n: int) -> None:
     lib().so_set_threads(int(n))
+
+
+@contextlib.contextmanager
+def libm_mode():
+    """Test-only: inside the block powf / cosf / sinf are libm's, as in the
+    reference's text (so_set_libm); the default definition is restored after."""
+    lib().so_set_libm(1)
+    try:
+        yield
+    finally:
+        lib().so_set_libm(0)
 
 
 def gaussian_kernel(sigma: float) -> np.ndarray:

@@ -11,12 +11,17 @@
  * hal::exp32f, hal::fastAtan2, hal::magnitude32f, Matx33f::solve(DECOMP_LU),
  * resize(INTER_NEAREST)) as documented in SURVEY.md Appendix A.
  *
- * PARITY UNPINNED: the reference cannot be compiled in this image (it needs
- * OpenCV 4.0 + opencv_contrib, which are absent, and stand-in headers are not
- * allowed), and it ships no tests, golden vectors or known-answer fixtures.
- * The restatement is therefore checked only against independent math
- * (numpy double-precision re-derivations of each helper) and the fixtures in
- * tests/golden/ are regression vectors produced by this oracle.
+ * PINNED TO THE REFERENCE'S SOURCE: src/sift.cpp's own text, compiled with its
+ * makefile's flags over stand-in OpenCV primitives (oracle/cvmini/,
+ * oracle/ref_build.py), is compared with this restatement bit for bit in
+ * tests/test_reference_source.py, and its recorded outputs
+ * (tests/golden/ref_*.npz) with the GPU.  They agree on every plane and every
+ * keypoint field; the only differences are the libm calls (powf, cosf, sinf)
+ * that sift_oracle.c replaces on purpose.  NOT pinned: the OpenCV primitives
+ * themselves (both sides restate them from SURVEY.md Appendix A), SIMD
+ * dispatch inside real OpenCV, the front end's resize, BFMatcher,
+ * findHomography.  The other fixtures in tests/golden/ are vectors produced
+ * by this oracle.
  *
  * Arithmetic contract: compiled with -O2 -ffp-contract=off, no -march, no
  * -ffast-math -- the reference's own makefile:25 flags (-O3, no -march) give
@@ -119,6 +124,13 @@ void so_free(void* p);
 
 /* Number of OpenMP threads for the descriptor loop (src/sift.cpp:738). */
 void so_set_threads(int n);
+
+/* Test-only switch, off by default (0): when on, powf (src/sift.cpp:384) and
+ * cosf / sinf (:583-584) are libm's, as in the reference's text, instead of
+ * (float)f((double)x).  Used only to compare this file with the reference's own
+ * source byte for byte; so_helper ops 3-5 keep the default definition. */
+void so_set_libm(int on);
+int so_get_libm(void);
 
 /* Synthetic integer-exact test image, SURVEY.md 8(d) row d2. */
 void so_synth_image(int b, int rows, int cols, float* out);

@@ -15,9 +15,9 @@ What is made, and from what:
                   inputs: keypoints (cv::KeyPoint records), descriptors, and
                   SHA-256 digests of every Gaussian / DoG plane.
 
-PARITY UNPINNED: the reference itself cannot be built in this image (OpenCV
-4.0 + contrib absent) and ships no golden vectors, so these are regression
-vectors of the restatement, not reference outputs.  Only data is stored
+These are vectors of the restatement, not reference outputs; outputs of the
+reference's own source are recorded by make_ref_golden.py (ref_*.npz), and
+tests/test_reference_source.py compares the two.  Only data is stored
 (numpy arrays, np.load(allow_pickle=False)).
 """
 import hashlib

@@ -1,7 +1,11 @@
 """CPU tests of the oracle (oracle/sift_oracle.c): each OpenCV helper it
 restates is checked against an independent numpy/double re-derivation, the
 whole path against the committed golden fixtures, plus size-independent
-properties.  PARITY UNPINNED vs the real reference (see sift_oracle.h)."""
+properties.  The oracle against the reference's own src/sift.cpp, compiled
+with its makefile's flags over stand-in OpenCV primitives, is in
+test_reference_source.py; still unpinned are the OpenCV primitives themselves,
+SIMD dispatch inside real OpenCV, the front end's resize, BFMatcher and
+findHomography (see sift_oracle.h)."""
 import math
 import os
 

@@ -206,7 +206,12 @@ int sift_multi_stats(const sift_multi* m, long long* steps, long long* records, 
 int sift_multi_rccl_version(void);
 
 /* ---- sub-module entry points (host memory, synchronous) ----------------- */
-/* Gaussian_Blur (include/sift.hpp:47, src/sift.cpp:123-153). */
+/* Gaussian_Blur (include/sift.hpp:47, src/sift.cpp:123-153).  Both blurs take
+ * 0 < sigma <= 100 (SIFT_E_INVALID otherwise, NaN included), kernel half-width
+ * w = floor(3 sigma) in 0 .. 300.  w = 0 is the reference's own arithmetic: the
+ * 2-D blur multiplies by the single tap 1 / (2 pi sigma^2), the 1-D blur's tap
+ * loop is empty and the result is all zeros; a plane with one row or one
+ * column blurs to zeros (the getSubMatrix border rule, :116). */
 int sift_gaussian_blur(sift_ctx* ctx, const float* src, int rows, int cols, double sigma,
                        float* dst);
 /* Gaussian_Blur_1D (include/sift.hpp:49, src/sift.cpp:170-217). */
@@ -224,7 +229,17 @@ int sift_build_dog_pyramid(sift_ctx* ctx, const float* gpyr, int rows, int cols,
 int sift_find_scale_space_extrema(sift_ctx* ctx, const float* gpyr, const float* dog, int rows,
                                   int cols, int n_octaves, sift_keypoint* kpts, int cap,
                                   int* n_out);
-/* calDescriptor (include/sift.hpp:64, src/sift.cpp:733-753). */
+/* calDescriptor (include/sift.hpp:64, src/sift.cpp:733-753).  A keypoint's
+ * octave byte is signed (254 = -2); with oi = octave - first_octave, a row with
+ * oi < 0, oi >= n_octaves or layer > 4 makes the call return SIFT_E_INVALID
+ * (the CV_Assert of :744, and the bounds of gpyr it does not check).  Angles in
+ * [0, 720] are the reference's contract: its single wrap of the orientation bin
+ * covers 360 - angle in [-360, 360], and beyond that it adds samples outside
+ * their histogram cell.  The library wraps the bin modulo 8 (the circular
+ * histogram) for every angle, which is the reference's result inside the
+ * contract; outside it the call succeeds, the row's descriptor is that
+ * histogram's, and other rows are not affected.  NaN angles give an
+ * unspecified (in-bounds) bin. */
 int sift_calc_descriptors(sift_ctx* ctx, const float* gpyr, int rows, int cols, int n_octaves,
                           const sift_keypoint* kpts, int n, float* desc, int first_octave);
 
@@ -234,7 +249,9 @@ int sift_calc_descriptors(sift_ctx* ctx, const float* gpyr, int rows, int cols, 
  * optional INTER_LINEAR resize to out_rows x out_cols (the scene's
  * Size(960, 960); no resize when the sizes are equal) -> cvtColor
  * COLOR_RGB2GRAY on those BGR bytes -> CV_32F.  Decoding stays with the
- * caller.  Host buffers (synchronous), gray is out_rows x out_cols floats: */
+ * caller.  Host buffers (synchronous), gray is out_rows x out_cols floats;
+ * rows are row_stride >= 3 * cols bytes apart and only the
+ * (rows - 1) * row_stride + 3 * cols bytes a strided view owns are read: */
 int sift_bgr8_to_gray(sift_ctx* ctx, const uint8_t* bgr, int rows, int cols, size_t row_stride, int out_rows,
                       int out_cols, float* gray);
 /* Device buffers, a batch of images, enqueued on the context stream (the

@@ -47,12 +47,22 @@ def _taps(n_out: int, n_in: int, clamp: bool):
     return s, a0, a1
 
 
-def resize_linear_u8(img: np.ndarray, out_rows: int, out_cols: int) -> np.ndarray:
-    """cv::resize(img, dst, Size(out_cols, out_rows)), INTER_LINEAR, 8UC3."""
+def vertical_tail(out_cols: int, cn: int = 3) -> int:
+    """First element of an output row that VResizeLinearVec_32s8u leaves to the scalar tail: its
+    16-lane loop, then 8-lane steps while more than 8 elements remain."""
+    n = out_cols * cn
+    vtail = n // 16 * 16
+    while vtail < n - 8:
+        vtail += 8
+    return vtail
+
+
+def vertical_forms(img: np.ndarray, out_rows: int, out_cols: int):
+    """(simd, scalar, vtail): the resized image [out_rows, out_cols, cn] with every element through the
+    16-bit mul_hi form, with every element through FixedPtCast, and the element index of a row at which
+    the real resize switches from the first to the second."""
     src = np.asarray(img, np.uint8)
     h, w, cn = src.shape
-    if (h, w) == (out_rows, out_cols):
-        return src.copy()
     sx, ax0, ax1 = _taps(out_cols, w, clamp=True)
     sy, by0, by1 = _taps(out_rows, h, clamp=False)
     sx1 = np.minimum(sx + 1, w - 1)
@@ -68,13 +78,19 @@ def resize_linear_u8(img: np.ndarray, out_rows: int, out_cols: int) -> np.ndarra
     simd = (((h0 >> 4) * b0) >> 16) + (((h1 >> 4) * b1) >> 16)
     simd = (simd + 2) >> 2
     scal = (h0 * b0 + h1 * b1 + (1 << 21)) >> 22
-    n = out_cols * cn
-    vtail = n // 16 * 16
-    while vtail < n - 8:
-        vtail += 8
+    return (np.clip(simd, 0, 255).astype(np.uint8), np.clip(scal, 0, 255).astype(np.uint8),
+            vertical_tail(out_cols, cn))
+
+
+def resize_linear_u8(img: np.ndarray, out_rows: int, out_cols: int) -> np.ndarray:
+    """cv::resize(img, dst, Size(out_cols, out_rows)), INTER_LINEAR, 8UC3."""
+    src = np.asarray(img, np.uint8)
+    h, w, cn = src.shape
+    if (h, w) == (out_rows, out_cols):
+        return src.copy()
+    simd, scal, vtail = vertical_forms(src, out_rows, out_cols)
     elem = (np.arange(out_cols)[:, None] * cn + np.arange(cn)[None, :])[None]
-    v = np.where(elem < vtail, simd, scal)
-    return np.clip(v, 0, 255).astype(np.uint8)
+    return np.where(elem < vtail, simd, scal)
 
 
 def rgb2gray_on_bgr(img: np.ndarray) -> np.ndarray:

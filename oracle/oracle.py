@@ -64,6 +64,7 @@ def lib():
         L.so_set_threads.argtypes = [ctypes.c_int]
         L.so_set_libm.argtypes = [ctypes.c_int]
         L.so_get_libm.restype = ctypes.c_int
+        L.so_set_wrap_mod.argtypes = [ctypes.c_int]
         L.so_synth_image.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, fp]
         L.so_exp32f.argtypes = [fp, fp, ctypes.c_int]
         L.so_fast_atan2.argtypes = [fp, fp, fp, ctypes.c_int]
@@ -115,6 +116,17 @@ def libm_mode():
         yield
     finally:
         lib().so_set_libm(0)
+
+
+@contextlib.contextmanager
+def circular_bins():
+    """Test-only: inside the block calc_descriptors wraps the orientation bin modulo 8 (so_set_wrap_mod),
+    the library's definition for a caller angle outside [0, 720]; identical inside that range."""
+    lib().so_set_wrap_mod(1)
+    try:
+        yield
+    finally:
+        lib().so_set_wrap_mod(0)
 
 
 def gaussian_kernel(sigma: float) -> np.ndarray:

@@ -5,8 +5,10 @@
  *
  * Signatures and packed layouts mirror the so_* functions of sift_oracle.h,
  * so that oracle/refsrc.py and oracle/oracle.py are interchangeable in a
- * test.  Only 5 octaves: src/sift.cpp:248 indexes gpyr[o*nOctaves + i], which
- * is right only when nOctaves == nScales.
+ * test.  buildGaussianPyramid and SIFT_NCL with 5 octaves only: src/sift.cpp:248
+ * indexes gpyr[o*nOctaves + i], which is right only when nOctaves == nScales.
+ * buildDoGPyramid, findScaleSpaceExtrema and calDescriptor index by nScales and
+ * take any count of 1 .. 12 octaves.
  */
 #include "sift.hpp"
 
@@ -15,7 +17,7 @@
 
 namespace {
 
-const int kScales = 5, kDog = 4;
+const int kScales = 5, kDog = 4, kMaxOctaves = 12;
 
 void cap_threads() {
   if (omp_get_max_threads() > 16) omp_set_num_threads(16);
@@ -84,7 +86,7 @@ int rs_build_gaussian_pyramid(const float* img, int rows, int cols, int n_octave
 }
 
 int rs_build_dog_pyramid(const float* gpyr, int rows, int cols, int n_octaves, float* dog) {
-  if (n_octaves != kScales) return -1;
+  if (n_octaves < 1 || n_octaves > kMaxOctaves) return -1;
   cap_threads();
   std::vector<Mat> g = views(gpyr, rows, cols, n_octaves, kScales), d;
   buildDoGPyramid(g, d, n_octaves);
@@ -93,10 +95,10 @@ int rs_build_dog_pyramid(const float* gpyr, int rows, int cols, int n_octaves, f
 }
 
 /* Writes up to cap keypoints; returns the count found (may exceed cap), -1 for
- * an octave count other than 5. */
+ * an octave count outside 1 .. 12. */
 int rs_find_scale_space_extrema(const float* gpyr, const float* dog, int rows, int cols, int n_octaves,
                                 rs_keypoint* kps, int cap) {
-  if (n_octaves != kScales) return -1;
+  if (n_octaves < 1 || n_octaves > kMaxOctaves) return -1;
   cap_threads();
   std::vector<Mat> g = views(gpyr, rows, cols, n_octaves, kScales);
   std::vector<Mat> d = views(dog, rows, cols, n_octaves, kDog);
@@ -109,7 +111,7 @@ int rs_find_scale_space_extrema(const float* gpyr, const float* dog, int rows, i
 
 int rs_calc_descriptors(const float* gpyr, int rows, int cols, int n_octaves, const rs_keypoint* kps, int n,
                         float* desc, int first_octave) {
-  if (n_octaves != kScales) return -1;
+  if (n_octaves < 1 || n_octaves > kMaxOctaves) return -1;
   cap_threads();
   std::vector<Mat> g = views(gpyr, rows, cols, n_octaves, kScales);
   std::vector<KeyPoint> k((size_t)n);

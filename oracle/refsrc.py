@@ -3,8 +3,10 @@ src/sift.cpp compiled over the stand-in headers of oracle/cvmini/ (recipe:
 oracle/ref_build.py, entry points: oracle/ref_wrap.cpp).
 
 TEST INFRASTRUCTURE ONLY.  Same function names and packed layouts as
-oracle/oracle.py, so the two are interchangeable in a test.  Five octaves
-only (src/sift.cpp:248 is right only when nOctaves == nScales).
+oracle/oracle.py, so the two are interchangeable in a test.  build_gaussian_pyramid
+and sift with five octaves only (src/sift.cpp:248 is right only when
+nOctaves == nScales); the DoG, extrema and descriptor functions index by
+nScales and take any octave count.
 """
 from __future__ import annotations
 
@@ -107,14 +109,12 @@ def build_gaussian_pyramid(img: np.ndarray, n_octaves: int = 5) -> np.ndarray:
 
 
 def build_dog_pyramid(gpyr: np.ndarray, rows: int, cols: int, n_octaves: int = 5) -> np.ndarray:
-    _five(n_octaves)
     out = np.empty(_plane_total(rows, cols, n_octaves, 4), np.float32)
     assert lib().rs_build_dog_pyramid(_fp(gpyr), rows, cols, n_octaves, _fp(out)) == 0
     return out
 
 
 def find_scale_space_extrema(gpyr, dog, rows, cols, n_octaves=5) -> np.ndarray:
-    _five(n_octaves)
     cap = 1 << 14
     while True:
         kps = np.zeros(cap, KEYPOINT_DTYPE)
@@ -126,7 +126,6 @@ def find_scale_space_extrema(gpyr, dog, rows, cols, n_octaves=5) -> np.ndarray:
 
 
 def calc_descriptors(gpyr, rows, cols, kps: np.ndarray, n_octaves=5, first_octave=0) -> np.ndarray:
-    _five(n_octaves)
     kps = np.ascontiguousarray(kps, KEYPOINT_DTYPE)
     out = np.zeros((len(kps), 128), np.float32)
     if len(kps):

@@ -66,6 +66,12 @@ static inline float sinf_def(float x) { return (float)sin((double)x); }
 static int g_libm = 0;
 void so_set_libm(int on) { g_libm = on != 0; }
 int so_get_libm(void) { return g_libm; }
+/* Test-only: wrap the descriptor's orientation bin modulo n (the circular histogram, what the
+ * library defines for a caller angle outside [0, 720]) instead of the reference's single wrap,
+ * which leaves o0 outside 0 .. n-1 there and adds the sample outside its histogram cell.  The
+ * two are the same for every angle in [0, 720]. */
+static int g_wrap_mod = 0;
+void so_set_wrap_mod(int on) { g_wrap_mod = on != 0; }
 static inline float pow2f_cr(float y) { return g_libm ? powf(2.f, y) : pow2f_def(y); }
 static inline float cosf_cr(float x) { return g_libm ? cosf(x) : cosf_def(x); }
 static inline float sinf_cr(float x) { return g_libm ? sinf(x) : sinf_def(x); }
@@ -695,8 +701,12 @@ static void sift_descriptor(const float* img, int nrows, int ncols, float ptx, f
     rbin -= r0;
     cbin -= c0;
     obin -= o0;
-    if (o0 < 0) o0 += n;
-    if (o0 >= n) o0 -= n;
+    if (g_wrap_mod) {
+      o0 = ((o0 % n) + n) % n;
+    } else {
+      if (o0 < 0) o0 += n;
+      if (o0 >= n) o0 -= n;
+    }
     float v_r1 = mag * rbin, v_r0 = mag - v_r1;
     float v_rc11 = v_r1 * cbin, v_rc10 = v_r1 - v_rc11;
     float v_rc01 = v_r0 * cbin, v_rc00 = v_r0 - v_rc01;

@@ -131,6 +131,8 @@ void so_set_threads(int n);
  * source byte for byte; so_helper ops 3-5 keep the default definition. */
 void so_set_libm(int on);
 int so_get_libm(void);
+/* Test-only: the descriptor's orientation bin wrapped modulo n (circular) instead of once. */
+void so_set_wrap_mod(int on);
 
 /* Synthetic integer-exact test image, SURVEY.md 8(d) row d2. */
 void so_synth_image(int b, int rows, int cols, float* out);

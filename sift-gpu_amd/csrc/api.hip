@@ -1529,7 +1529,9 @@ int sift_bgr8_to_gray(sift_ctx* c, const uint8_t* bgr, int rows, int cols, size_
   if (rc) return rc;
   uint8_t* d_src = static_cast<uint8_t*>(c->d_match);
   float* d_out = reinterpret_cast<float*>(static_cast<char*>(c->d_match) + sb);
-  HIP_TRY(c, hipMemcpyAsync(d_src, bgr, (size_t)rows * row_stride, hipMemcpyHostToDevice, c->stream));
+  // a strided view (an ROI) owns no padding after its last row: copy only what the image owns
+  const size_t owned = (size_t)(rows - 1) * row_stride + (size_t)cols * 3;
+  HIP_TRY(c, hipMemcpyAsync(d_src, bgr, owned, hipMemcpyHostToDevice, c->stream));
   if ((rc = sift_bgr8_to_gray_device(c, d_src, 1, rows, cols, row_stride, 0, out_rows, out_cols, d_out,
                                      (size_t)out_cols * sizeof(float), 0)))
     return rc;

@@ -446,9 +446,12 @@ descriptor_kernel(DescArgs A) {
         static_assert(kDescBins == 8, "o0 & 7 is the wrap for 8 bins");
         O0 = o0 & 7;
       } else {
-        if (o0 < 0) o0 += nb;
-        if (o0 >= nb) o0 -= nb;
-        O0 = ok ? o0 : 0;
+        // a caller's angle is unchecked: ori in [-360, 360] (angle in [0, 720]) leaves o0
+        // in [-8, 16], where the reference's two wraps are o0 & 7 as above; any other
+        // angle (NaN included) is wrapped the same way, so that the bin, and the LDS
+        // address built from it, stays in 0 .. 7 (sift_hip.h: the circular histogram)
+        static_assert(kDescBins == 8, "o0 & 7 is the wrap for 8 bins");
+        O0 = ok ? (o0 & 7) : 0;
       }
       const int X = L.X, Y = L.Y, Rm = X - 1, Cm = Y - 1;  // Rm, Cm: the unpacked form only
       const int odd = ((Rm & 1) << 2) | ((Cm & 1) << 1) | (O0 & 1);

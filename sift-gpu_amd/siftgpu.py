@@ -318,17 +318,28 @@ class Context:
                                                   _fp(desc), firstOctave))
         return desc
 
-    def bgr8_to_gray(self, bgr: np.ndarray, out_rows: int | None = None, out_cols: int | None = None):
+    def bgr8_to_gray(self, bgr: np.ndarray, out_rows: int | None = None, out_cols: int | None = None,
+                     row_stride: int | None = None):
         """readImage's conversion (src/main.cpp:83-85) of decoded BGR bytes:
-        optional INTER_LINEAR resize, COLOR_RGB2GRAY on BGR, CV_32F."""
-        bgr = np.ascontiguousarray(bgr, np.uint8)
+        optional INTER_LINEAR resize, COLOR_RGB2GRAY on BGR, CV_32F.
+        row_stride None: bgr is copied to a packed array.  A number: bgr's own
+        memory is passed with that row stride in bytes (an H x W x 3 uint8 view,
+        such as an ROI, with packed pixels and rows that far apart); only the
+        (H - 1) * row_stride + 3 * W bytes the view owns are read."""
+        if row_stride is None:
+            bgr = np.ascontiguousarray(bgr, np.uint8)
         if bgr.ndim != 3 or bgr.shape[2] != 3:
             raise ValueError("expected an H x W x 3 uint8 BGR image")
         r, c = bgr.shape[:2]
+        if row_stride is None:
+            row_stride = c * 3
+        elif (bgr.dtype != np.uint8 or bgr.strides[1:] != (3, 1) or row_stride < c * 3
+              or (r > 1 and bgr.strides[0] != row_stride)):
+            raise ValueError("bgr must be an H x W x 3 uint8 view with packed pixels and rows row_stride bytes apart")
         orows, ocols = out_rows or r, out_cols or c
         gray = np.empty((orows, ocols), np.float32)
         self._check("sift_bgr8_to_gray",
-                    self._L.sift_bgr8_to_gray(self.h, bgr.ctypes.data, r, c, c * 3, orows, ocols, _fp(gray)))
+                    self._L.sift_bgr8_to_gray(self.h, bgr.ctypes.data, r, c, row_stride, orows, ocols, _fp(gray)))
         return gray
 
     def bgr8_to_gray_device(self, src_ptr: int, batch: int, rows: int, cols: int, row_stride: int,

@@ -43,3 +43,21 @@ def expected_device_descriptors(g):
     d = g["desc"].copy()
     d[g["libm_rows"]] = g["desc_def"]
     return d
+
+
+def args_image_fixture(key):
+    """(g, k) of tests/golden/ref_args_img_<key>.npz: g holds the plane digests, k the keypoints and
+    descriptors (another file of the family where the same bytes were recorded for a smaller octave count)."""
+    g = load_golden("ref_args_img_" + key)
+    return g, (load_golden(str(g["same_as"])) if "same_as" in g.files else g)
+
+
+def check_fixture_descriptors(desc, k, what):
+    """desc against the descriptors of a ref_args_img_* fixture: every byte, or, where the file holds
+    only their digest (more than 500 rows), the digest and the rows of octaves 4 and up in full."""
+    from conftest import assert_bits_equal, sha
+    if "desc" in k.files:
+        assert_bits_equal(desc, expected_device_descriptors(k), what)
+    else:
+        assert_bits_equal(desc[k["desc_rows"]], k["desc_rows_bytes"], what + " (octaves 4 and up)")
+        assert sha(desc) == str(k["desc_sha"]), what + ": digest"

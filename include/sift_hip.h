@@ -266,8 +266,12 @@ int sift_bgr8_to_gray_device(sift_ctx* ctx, const uint8_t* d_bgr, int batch, int
  * stays with the caller).  query [n_query][128], train [n_train][128] floats;
  * for each query the k (1 or 2) nearest train rows by float L1 distance
  * (OpenCV normL1_ summation order, see match.hip), ascending, an earlier train
- * index first at equal distance.  idx / dist are [n_query][k]; when
- * n_train < k the missing entries are idx -1, dist +inf.
+ * index first at equal distance.  idx / dist are [n_query][k].  A train row
+ * whose distance overflowed to +inf is never a neighbour: where fewer than k
+ * train rows are at a finite distance (n_train < k included) the missing
+ * entries are idx -1, dist +inf, and the ratio stage below skips such a query.
+ * This is the library's own rule; descriptors that produce NaN distances (NaN
+ * or infinite elements) are unspecified.  Denormal values are not flushed.
  * Host buffers (synchronous): */
 int sift_knn_match_l1(sift_ctx* ctx, const float* query, int n_query, const float* train, int n_train, int k,
                       int* idx, float* dist);

@@ -45,7 +45,10 @@ def l1_distances(query: np.ndarray, train: np.ndarray, block: int = 256) -> np.n
 
 def knn_match(query: np.ndarray, train: np.ndarray, k: int = 2):
     """(idx, dist) [n_query, k]: the k nearest train rows per query, ascending,
-    earlier index first at equal distance; idx -1 / dist +inf where n_train < k."""
+    earlier index first at equal distance.  A train row whose distance
+    overflowed to +inf is never a neighbour (this library's rule, sift_hip.h):
+    idx -1 / dist +inf where fewer than k train rows are at a finite distance,
+    n_train < k included.  NaN is unspecified."""
     assert k in (1, 2)
     nq, nt = len(query), len(train)
     idx = np.full((nq, k), -1, np.int32)
@@ -55,8 +58,8 @@ def knn_match(query: np.ndarray, train: np.ndarray, k: int = 2):
     d = l1_distances(query, train)
     order = np.argsort(d, axis=1, kind="stable")[:, :k]   # stable: ties keep index order
     m = order.shape[1]
-    idx[:, :m] = order
     dist[:, :m] = np.take_along_axis(d, order, axis=1)
+    idx[:, :m] = np.where(dist[:, :m] == np.inf, -1, order)
     return idx, dist
 
 

@@ -44,6 +44,8 @@ struct Best2 {
 };
 
 // (d, i) < (e, j) lexicographically; i = -1 (empty slot) sorts last via d = +inf.
+// No index is below -1, so a candidate at d = +inf never displaces an empty
+// slot: such a row is never a neighbour (sift_hip.h).
 __device__ __forceinline__ bool lex_lt(float d, int i, float e, int j) { return d < e || (d == e && i < j); }
 
 __device__ __forceinline__ void insert(Best2& b, float d, int i) {

@@ -352,7 +352,8 @@ class Context:
 
     def knnMatch(self, query: np.ndarray, train: np.ndarray, k: int = 2):
         """BFMatcher(NORM_L1).knnMatch as arrays (src/main.cpp:25-27): idx, dist
-        [n_query, k]; idx -1 / dist +inf where there are fewer than k train rows."""
+        [n_query, k]; idx -1 / dist +inf where fewer than k train rows are at a
+        finite distance (a row at +inf is never a neighbour)."""
         q = np.ascontiguousarray(query, np.float32).reshape(-1, DESC_LEN)
         t = np.ascontiguousarray(train, np.float32).reshape(-1, DESC_LEN)
         idx = np.empty((len(q), k), np.int32)

@@ -1,0 +1,317 @@
+// apps.hip -- the application stages behind the C ABI (include/sift_hip.h):
+// the L1 kNN matcher, its segmented form, the ratio test with point pairs and
+// the BGR8 front end, each in a device and a host form, and the homography
+// wrappers.  Host code only; the kernels live in match.hip, frontend.hip and
+// homography.hip.  Every form carves its scratch from the context's one block
+// by a layout of scratch.hpp.
+#include "ctx.hpp"
+#include "scratch.hpp"
+
+using namespace sift;
+
+namespace {
+
+static_assert(kDescRow == kDescLen && sizeof(Float2) == sizeof(float2) && sizeof(Int2) == sizeof(int2),
+              "scratch.hpp restates these without the HIP headers");
+float2* dev(Float2* p) { return reinterpret_cast<float2*>(p); }
+int2* dev(Int2* p) { return reinterpret_cast<int2*>(p); }
+
+// Runs layout(Carver&) twice: on a null base to size the scratch block, then
+// on the block itself.
+template <typename S, typename F>
+int carve(sift_ctx* c, S* out, F&& layout) {
+  Carver measure(nullptr);
+  layout(measure);
+  if (int rc = ensure_match(c, measure.bytes())) return rc;
+  Carver real(c->d_match.get());
+  *out = layout(real);
+  return SIFT_OK;
+}
+
+bool rows_aligned(const float* query, const float* train) {
+  return !((reinterpret_cast<uintptr_t>(query) | reinterpret_cast<uintptr_t>(train)) & 15);
+}
+const char* const kRowsUnaligned = "descriptor rows must be 16-byte aligned";
+
+int clamp_off(int v, int cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
+
+// The check_* functions hold the argument checks that the device and the host
+// form of an entry point share, in the order they fire; a call with nothing to
+// do (no queries, no segments) passes them whatever its buffers.
+
+// ---- BFMatcher(NORM_L1).knnMatch, src/main.cpp:25-27 ----
+int check_knn(sift_ctx* c, const float* query, int n_query, const float* train, int n_train, int k, const int* idx,
+              const float* dist) {
+  if (!c) return SIFT_E_INVALID;
+  if (n_query < 0 || n_train < 0) return fail(c, SIFT_E_INVALID, "negative descriptor count");
+  if (k != 1 && k != 2) return fail(c, SIFT_E_INVALID, "k must be 1 or 2");
+  if (n_query == 0) return SIFT_OK;
+  if (!query || !idx || !dist || (n_train > 0 && !train)) return fail(c, SIFT_E_INVALID, "null buffer");
+  return SIFT_OK;
+}
+
+int knn_device(sift_ctx* c, const float* q, int nq, const float* t, int nt, int k, int splits, int* idx, float* dist,
+               KnnParts parts) {
+  {
+    StageScope s(c, ST_MATCH, 2.0 * kDescLen * nq * (double)nt, 512.0 * (nq + (double)nt));
+    launch_knn_l1(c->stream, q, nq, t, nt, k, splits, dev(parts.dist), dev(parts.idx), idx, dist);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
+// ---- a whole batch: segmented knnMatch, ratio test, point pairs (src/main.cpp:25-52) ----
+int check_seg(sift_ctx* c, const float* query, const int* q_offsets, int n_segments, int q_cap, const float* train,
+              int t_cap, int k, const int* idx, const float* dist) {
+  if (!c) return SIFT_E_INVALID;
+  if (n_segments < 0 || q_cap < 0 || t_cap < 0) return fail(c, SIFT_E_INVALID, "negative count");
+  if (k != 1 && k != 2) return fail(c, SIFT_E_INVALID, "k must be 1 or 2");
+  if (n_segments == 0 || q_cap == 0) return SIFT_OK;
+  if (!query || !q_offsets || !idx || !dist || (t_cap > 0 && !train)) return fail(c, SIFT_E_INVALID, "null buffer");
+  return SIFT_OK;
+}
+
+int knn_seg_device(sift_ctx* c, const float* q, const int* qoff, int n_segments, int q_cap, const float* t,
+                   const int* toff, int t_cap, int k, int splits, int* idx, float* dist, SegParts s) {
+  {
+    StageScope sc(c, ST_MATCH_SEG);  // the work depends on offsets only the device knows
+    launch_knn_l1_seg(c->stream, q, qoff, n_segments, q_cap, t, toff, t_cap, k, splits, s.tile_start,
+                      dev(s.parts.dist), dev(s.parts.idx), idx, dist);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
+// t_cap: the host form's train keypoint count (the device form never reads it: 0).
+int check_ratio(sift_ctx* c, const int* idx, const float* dist, const int* q_offsets, int n_segments, int q_cap,
+                const sift_keypoint* q_kpts, const sift_keypoint* t_kpts, int t_cap, const sift_match* matches,
+                const float* src_xy, const float* dst_xy, int m_cap, const int* m_offsets) {
+  if (!c) return SIFT_E_INVALID;
+  if (n_segments < 0 || q_cap < 0 || m_cap < 0 || (q_kpts && t_cap < 0))
+    return fail(c, SIFT_E_INVALID, "negative count");
+  if (n_segments == 0 || q_cap == 0) return SIFT_OK;
+  if (!idx || !dist || !q_offsets || !m_offsets || (m_cap > 0 && !matches))
+    return fail(c, SIFT_E_INVALID, "null buffer");
+  if (q_kpts && (!t_kpts || (m_cap > 0 && (!src_xy || !dst_xy))))
+    return fail(c, SIFT_E_INVALID, "point pairs need the train keypoints and both xy buffers");
+  return SIFT_OK;
+}
+
+int ratio_device(sift_ctx* c, const int* idx, const float* dist, const int* qoff, int n_segments, int q_cap,
+                 double ratio, const sift_keypoint* q_kpts, const sift_keypoint* t_kpts, const int* toff,
+                 sift_match* matches, float* src_xy, float* dst_xy, int m_cap, int* moff, int* blk_scan) {
+  {
+    StageScope sc(c, ST_RATIO, 0, 16.0 * q_cap);
+    launch_ratio_matches(c->stream, idx, dist, qoff, n_segments, q_cap, ratio, q_kpts, t_kpts, toff, matches,
+                         src_xy, dst_xy, m_cap, moff, blk_scan);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
+// ---- readImage front end, src/main.cpp:79-87 ----
+int check_bgr(sift_ctx* c, const void* bgr, int batch, int rows, int cols, int out_rows, int out_cols,
+              const void* gray) {
+  if (!c) return SIFT_E_INVALID;
+  if (!bgr || !gray) return fail(c, SIFT_E_INVALID, "null buffer");
+  if (batch < 1 || rows < 1 || cols < 1 || out_rows < 1 || out_cols < 1)
+    return fail(c, SIFT_E_INVALID, "empty image");
+  return SIFT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sift_knn_match_l1_device(sift_ctx* c, const float* d_query, int n_query, const float* d_train, int n_train,
+                             int k, int* d_idx, float* d_dist) {
+  int rc = check_knn(c, d_query, n_query, d_train, n_train, k, d_idx, d_dist);
+  if (rc || n_query == 0) return rc;
+  if (!rows_aligned(d_query, d_train)) return fail(c, SIFT_E_INVALID, kRowsUnaligned);
+  (void)hipSetDevice(c->device);
+  const int splits = knn_splits(n_query, n_train);
+  KnnParts parts;
+  if ((rc = carve(c, &parts, [&](Carver& a) { return knn_layout(a, n_query, splits); }))) return rc;
+  return knn_device(c, d_query, n_query, d_train, n_train, k, splits, d_idx, d_dist, parts);
+}
+
+int sift_knn_match_l1(sift_ctx* c, const float* query, int n_query, const float* train, int n_train, int k,
+                      int* idx, float* dist) {
+  int rc = check_knn(c, query, n_query, train, n_train, k, idx, dist);
+  if (rc || n_query == 0) return rc;
+  (void)hipSetDevice(c->device);
+  const int splits = knn_splits(n_query, n_train);
+  KnnHost S;
+  if ((rc = carve(c, &S, [&](Carver& a) { return knn_host_layout(a, n_query, n_train, k, splits); }))) return rc;
+  const size_t row = kDescLen * sizeof(float);
+  HIP_TRY(c, hipMemcpyAsync(S.query, query, n_query * row, hipMemcpyHostToDevice, c->stream));
+  if (n_train) HIP_TRY(c, hipMemcpyAsync(S.train, train, n_train * row, hipMemcpyHostToDevice, c->stream));
+  if ((rc = knn_device(c, S.query, n_query, S.train, n_train, k, splits, S.idx, S.dist, S.parts))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(idx, S.idx, (size_t)n_query * k * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(dist, S.dist, (size_t)n_query * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SIFT_OK;
+}
+
+int sift_knn_match_l1_segmented_device(sift_ctx* c, const float* d_query, const int* d_q_offsets, int n_segments,
+                                       int q_cap, const float* d_train, const int* d_t_offsets, int t_cap, int k,
+                                       int* d_idx, float* d_dist) {
+  int rc = check_seg(c, d_query, d_q_offsets, n_segments, q_cap, d_train, t_cap, k, d_idx, d_dist);
+  if (rc || n_segments == 0 || q_cap == 0) return rc;
+  if (!rows_aligned(d_query, d_train)) return fail(c, SIFT_E_INVALID, kRowsUnaligned);
+  (void)hipSetDevice(c->device);
+  const int splits = knn_seg_splits(q_cap, n_segments, t_cap, d_t_offsets != nullptr);
+  SegParts S;
+  if ((rc = carve(c, &S, [&](Carver& a) { return seg_layout(a, n_segments, q_cap, splits); }))) return rc;
+  return knn_seg_device(c, d_query, d_q_offsets, n_segments, q_cap, d_train, d_t_offsets, t_cap, k, splits, d_idx,
+                        d_dist, S);
+}
+
+int sift_knn_match_l1_segmented(sift_ctx* c, const float* query, const int* q_offsets, int n_segments, int q_cap,
+                                const float* train, const int* t_offsets, int t_cap, int k, int* idx, float* dist) {
+  int rc = check_seg(c, query, q_offsets, n_segments, q_cap, train, t_cap, k, idx, dist);
+  if (rc || n_segments == 0 || q_cap == 0) return rc;
+  (void)hipSetDevice(c->device);
+  const int splits = knn_seg_splits(q_cap, n_segments, t_cap, t_offsets != nullptr);
+  SegHost S;
+  if ((rc = carve(c, &S, [&](Carver& a) {
+         return seg_host_layout(a, n_segments, q_cap, t_cap, t_offsets != nullptr, k, splits);
+       })))
+    return rc;
+  const size_t row = kDescLen * sizeof(float), ob = (size_t)(n_segments + 1) * sizeof(int);
+  HIP_TRY(c, hipMemcpyAsync(S.query, query, q_cap * row, hipMemcpyHostToDevice, c->stream));
+  if (t_cap) HIP_TRY(c, hipMemcpyAsync(S.train, train, t_cap * row, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.q_off, q_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  if (S.t_off) HIP_TRY(c, hipMemcpyAsync(S.t_off, t_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  if ((rc = knn_seg_device(c, S.query, S.q_off, n_segments, q_cap, S.train, S.t_off, t_cap, k, splits, S.idx, S.dist,
+                           S.seg)))
+    return rc;
+  // only the live rows come back: the others are left untouched, as in the device form
+  const int lo = clamp_off(q_offsets[0], q_cap), hi = clamp_off(q_offsets[n_segments], q_cap);
+  if (hi > lo) {
+    const size_t n = (size_t)(hi - lo) * k, o = (size_t)lo * k;
+    HIP_TRY(c, hipMemcpyAsync(idx + o, S.idx + o, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dist + o, S.dist + o, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SIFT_OK;
+}
+
+int sift_ratio_matches_device(sift_ctx* c, const int* d_idx, const float* d_dist, const int* d_q_offsets,
+                              int n_segments, int q_cap, double ratio, const sift_keypoint* d_q_kpts,
+                              const sift_keypoint* d_t_kpts, const int* d_t_offsets, sift_match* d_matches,
+                              float* d_src_xy, float* d_dst_xy, int m_cap, int* d_m_offsets) {
+  int rc = check_ratio(c, d_idx, d_dist, d_q_offsets, n_segments, q_cap, d_q_kpts, d_t_kpts, 0, d_matches, d_src_xy,
+                       d_dst_xy, m_cap, d_m_offsets);
+  if (rc || n_segments == 0 || q_cap == 0) return rc;
+  (void)hipSetDevice(c->device);
+  int* blk_scan = nullptr;
+  if ((rc = carve(c, &blk_scan, [&](Carver& a) { return ratio_layout(a, ratio_blocks(q_cap)); }))) return rc;
+  return ratio_device(c, d_idx, d_dist, d_q_offsets, n_segments, q_cap, ratio, d_q_kpts, d_t_kpts, d_t_offsets,
+                      d_matches, d_src_xy, d_dst_xy, m_cap, d_m_offsets, blk_scan);
+}
+
+int sift_ratio_matches(sift_ctx* c, const int* idx, const float* dist, const int* q_offsets, int n_segments,
+                       int q_cap, double ratio, const sift_keypoint* q_kpts, const sift_keypoint* t_kpts, int t_cap,
+                       const int* t_offsets, sift_match* matches, float* src_xy, float* dst_xy, int m_cap,
+                       int* m_offsets) {
+  int rc = check_ratio(c, idx, dist, q_offsets, n_segments, q_cap, q_kpts, t_kpts, t_cap, matches, src_xy, dst_xy,
+                       m_cap, m_offsets);
+  if (rc || n_segments == 0 || q_cap == 0) return rc;
+  (void)hipSetDevice(c->device);
+  RatioHost S;
+  if ((rc = carve(c, &S, [&](Carver& a) {
+         return ratio_host_layout(a, n_segments, q_cap, t_cap, m_cap, q_kpts != nullptr, t_offsets != nullptr,
+                                  ratio_blocks(q_cap));
+       })))
+    return rc;
+  const size_t ob = (size_t)(n_segments + 1) * sizeof(int);
+  HIP_TRY(c, hipMemcpyAsync(S.idx, idx, (size_t)q_cap * 2 * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.dist, dist, (size_t)q_cap * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.q_off, q_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  if (S.t_off) HIP_TRY(c, hipMemcpyAsync(S.t_off, t_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  if (q_kpts) {
+    HIP_TRY(c, hipMemcpyAsync(S.q_kpts, q_kpts, (size_t)q_cap * sizeof(sift_keypoint), hipMemcpyHostToDevice,
+                              c->stream));
+    if (t_cap)
+      HIP_TRY(c, hipMemcpyAsync(S.t_kpts, t_kpts, (size_t)t_cap * sizeof(sift_keypoint), hipMemcpyHostToDevice,
+                                c->stream));
+  }
+  if ((rc = ratio_device(c, S.idx, S.dist, S.q_off, n_segments, q_cap, ratio, S.q_kpts, S.t_kpts, S.t_off, S.matches,
+                         S.src_xy, S.dst_xy, m_cap, S.m_off, S.blk_scan)))
+    return rc;
+  HIP_TRY(c, hipMemcpyAsync(m_offsets, S.m_off, ob, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // only the written records come back
+  const size_t n = (size_t)(m_offsets[n_segments] < m_cap ? m_offsets[n_segments] : m_cap);
+  if (n) {
+    HIP_TRY(c, hipMemcpyAsync(matches, S.matches, n * sizeof(sift_match), hipMemcpyDeviceToHost, c->stream));
+    if (q_kpts) {
+      HIP_TRY(c, hipMemcpyAsync(src_xy, S.src_xy, n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(dst_xy, S.dst_xy, n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return SIFT_OK;
+}
+
+int sift_bgr8_to_gray_device(sift_ctx* c, const uint8_t* d_bgr, int batch, int rows, int cols, size_t row_stride,
+                             size_t img_stride, int out_rows, int out_cols, float* d_gray, size_t out_row_stride,
+                             size_t out_img_stride) {
+  if (int rc = check_bgr(c, d_bgr, batch, rows, cols, out_rows, out_cols, d_gray)) return rc;
+  if (row_stride < (size_t)cols * 3 || (batch > 1 && img_stride < row_stride * rows))
+    return fail(c, SIFT_E_INVALID, "source strides too small");
+  if (out_row_stride % sizeof(float) || out_img_stride % sizeof(float) ||
+      out_row_stride < (size_t)out_cols * sizeof(float) ||
+      (batch > 1 && out_img_stride < out_row_stride * out_rows))
+    return fail(c, SIFT_E_INVALID, "output strides");
+  (void)hipSetDevice(c->device);
+  {
+    StageScope s(c, ST_UPLOAD, 0, (3.0 * rows * cols + 4.0 * out_rows * out_cols) * batch);
+    launch_bgr8_gray(c->stream, d_bgr, (long long)row_stride, (long long)img_stride, rows, cols, d_gray,
+                     (long long)(out_row_stride / sizeof(float)), (long long)(out_img_stride / sizeof(float)),
+                     out_rows, out_cols, batch);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
+int sift_bgr8_to_gray(sift_ctx* c, const uint8_t* bgr, int rows, int cols, size_t row_stride, int out_rows,
+                      int out_cols, float* gray) {
+  int rc = check_bgr(c, bgr, 1, rows, cols, out_rows, out_cols, gray);
+  if (rc) return rc;
+  if (row_stride < (size_t)cols * 3) return fail(c, SIFT_E_INVALID, "row stride too small");
+  (void)hipSetDevice(c->device);
+  BgrHost S;  // the matcher's scratch doubles as staging here
+  if ((rc = carve(c, &S, [&](Carver& a) { return bgr_host_layout(a, rows, row_stride, out_rows, out_cols); })))
+    return rc;
+  // a strided view (an ROI) owns no padding after its last row: copy only what the image owns
+  const size_t owned = (size_t)(rows - 1) * row_stride + (size_t)cols * 3;
+  HIP_TRY(c, hipMemcpyAsync(S.src, bgr, owned, hipMemcpyHostToDevice, c->stream));
+  if ((rc = sift_bgr8_to_gray_device(c, S.src, 1, rows, cols, row_stride, 0, out_rows, out_cols, S.gray,
+                                     (size_t)out_cols * sizeof(float), 0)))
+    return rc;
+  HIP_TRY(c, hipMemcpyAsync(gray, S.gray, (size_t)out_rows * out_cols * sizeof(float), hipMemcpyDeviceToHost,
+                            c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SIFT_OK;
+}
+
+// ---- findHomography(RANSAC) + perspectiveTransform, src/main.cpp:54-62 ----
+int sift_find_homography(const float* src_xy, const float* dst_xy, int n, double ransac_thresh, int max_iters,
+                         double confidence, double* H, unsigned char* inlier_mask) {
+  if (!src_xy || !dst_xy || !H || n < 0) return SIFT_E_INVALID;
+  if (!find_homography_ransac(src_xy, dst_xy, n, ransac_thresh, max_iters, confidence, H, inlier_mask)) {
+    for (int i = 0; i < 9; ++i) H[i] = 0;  // OpenCV returns an empty Mat
+    return SIFT_E_INVALID;
+  }
+  return SIFT_OK;
+}
+
+int sift_perspective_transform(const double* H, const float* xy, int n, float* out_xy) {
+  if (!H || n < 0 || (n > 0 && (!xy || !out_xy))) return SIFT_E_INVALID;
+  perspective_transform(H, xy, n, out_xy);
+  return SIFT_OK;
+}
+
+}  // extern "C"

@@ -689,7 +689,7 @@ __global__ __launch_bounds__(64) void blur_sym_base_kernel(SymArgs A) {
 }
 
 bool sym_tables_match(const float* coefs) {
-  // api.hip's layout: the base table, then sig[1..4]'s, each (2w+1)^2 row-major
+  // ctx.hip's layout: the base table, then sig[1..4]'s, each (2w+1)^2 row-major
   const int ws[5] = {kSymW0, kSymW1, kSymW2, kSymW3, kSymW4};
   size_t at = 0;
   for (int t = 0; t < 5; ++t) {

@@ -1,7 +1,7 @@
 // gauss_host.hpp -- the Gaussian coefficients of SIFT_NCL, host side, no HIP.
 //
 // One definition shared by the library (the tables every blur kernel uses,
-// api.hip / blur.hip) and by gen_sym_coefs.cpp, which prints the same tables
+// ctx.hip / blur.hip) and by gen_sym_coefs.cpp, which prints the same tables
 // as compile-time constants for the symmetric octave blur (blur.hip).  The
 // library re-checks at context creation that the compiled-in tables equal the
 // ones it computes, entry for entry.

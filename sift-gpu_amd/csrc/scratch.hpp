@@ -1,0 +1,111 @@
+// scratch.hpp -- how the matcher and front-end entry points divide the
+// context's one scratch block (sift_ctx::d_match).  Each layout is described
+// once, as a function of a Carver, and run twice: on a null base to measure the
+// block, then on the block itself.  Plain host C++ (no HIP include), so that
+// tests/cpp/scratch_layout.cpp checks every layout without a GPU.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/sift_hip.h"
+
+namespace sift {
+
+// Bump allocator over one block: every piece starts on a 256-byte boundary.
+// On a null base it only measures (every pointer it returns is null).
+class Carver {
+ public:
+  struct Piece { size_t off, bytes; };
+  static constexpr size_t kAlign = 256;
+  static constexpr int kMaxPieces = 16;
+  Piece pieces[kMaxPieces] = {};  // what was taken so far, for the layout test
+  int n_pieces = 0;
+
+  explicit Carver(void* base) : base_(static_cast<char*>(base)) {}
+  template <typename T>
+  T* take(size_t count) {
+    const size_t at = bytes();
+    if (n_pieces < kMaxPieces) pieces[n_pieces++] = Piece{at, count * sizeof(T)};
+    end_ = at + count * sizeof(T);
+    return base_ ? reinterpret_cast<T*>(base_ + at) : nullptr;
+  }
+  template <typename T>
+  T* take_if(bool keep, size_t count) {  // the place is taken either way; null unless keep
+    T* p = take<T>(count);
+    return keep ? p : nullptr;
+  }
+  size_t bytes() const { return (end_ + kAlign - 1) / kAlign * kAlign; }
+
+ private:
+  char* base_;
+  size_t end_ = 0;
+};
+
+// A buffer the kernels index even when its count is 0 keeps one element.
+inline size_t at_least_one(int n) { return n > 0 ? (size_t)n : 1; }
+
+constexpr size_t kDescRow = 128;  // floats per descriptor (kDescLen)
+struct Float2 { float x, y; };    // layout of HIP's float2 / int2
+struct Int2 { int x, y; };
+
+// Every layout below takes its pieces in member order (a braced list is
+// evaluated left to right).
+
+// Per-split partial results of one kNN launch.
+struct KnnParts { Float2* dist; Int2* idx; };
+inline KnnParts knn_parts(Carver& a, size_t n) { return {a.take<Float2>(n), a.take<Int2>(n)}; }
+
+// sift_knn_match_l1_device: the partials of knn_splits() splits.
+inline KnnParts knn_layout(Carver& a, int n_query, int splits) { return knn_parts(a, (size_t)splits * n_query); }
+
+// sift_knn_match_l1: staged descriptors and results, then the partials.
+struct KnnHost { float *query, *train; int* idx; float* dist; KnnParts parts; };
+inline KnnHost knn_host_layout(Carver& a, int n_query, int n_train, int k, int splits) {
+  return {a.take<float>((size_t)n_query * kDescRow), a.take<float>(at_least_one(n_train) * kDescRow),
+          a.take<int>((size_t)n_query * k), a.take<float>((size_t)n_query * k), knn_layout(a, n_query, splits)};
+}
+
+// sift_knn_match_l1_segmented_device: the query-tile table, then the partials
+// of knn_seg_splits() splits (none for one split).
+struct SegParts { int* tile_start; KnnParts parts; };
+inline SegParts seg_layout(Carver& a, int n_segments, int q_cap, int splits) {
+  return {a.take<int>((size_t)n_segments + 1), knn_parts(a, splits > 1 ? (size_t)splits * q_cap : 0)};
+}
+
+// sift_knn_match_l1_segmented: t_off keeps its place when the caller has no
+// train offsets, and is null then.
+struct SegHost { float *query, *train; int* idx; float* dist; int *q_off, *t_off; SegParts seg; };
+inline SegHost seg_host_layout(Carver& a, int n_segments, int q_cap, int t_cap, bool has_t_off, int k, int splits) {
+  return {a.take<float>((size_t)q_cap * kDescRow), a.take<float>(at_least_one(t_cap) * kDescRow),
+          a.take<int>((size_t)q_cap * k),          a.take<float>((size_t)q_cap * k),
+          a.take<int>((size_t)n_segments + 1),     a.take_if<int>(has_t_off, (size_t)n_segments + 1),
+          seg_layout(a, n_segments, q_cap, splits)};
+}
+
+// sift_ratio_matches_device: the block scan of ratio_blocks() blocks.
+inline int* ratio_layout(Carver& a, int blocks) { return a.take<int>((size_t)blocks + 1); }
+
+// sift_ratio_matches: the staged kNN results and offsets, the keypoints and
+// point pairs only when the caller asks for pairs, the records, the block scan.
+struct RatioHost {
+  int* idx; float* dist; int *q_off, *t_off, *m_off; sift_keypoint *q_kpts, *t_kpts; sift_match* matches;
+  float *src_xy, *dst_xy; int* blk_scan;
+};
+inline RatioHost ratio_host_layout(Carver& a, int n_segments, int q_cap, int t_cap, int m_cap, bool pairs,
+                                   bool has_t_off, int blocks) {
+  const size_t offs = (size_t)n_segments + 1, m = at_least_one(m_cap);
+  return {a.take<int>((size_t)q_cap * 2), a.take<float>((size_t)q_cap * 2), a.take<int>(offs),
+          a.take_if<int>(has_t_off, offs), a.take<int>(offs),
+          pairs ? a.take<sift_keypoint>((size_t)q_cap) : nullptr,
+          pairs ? a.take<sift_keypoint>(at_least_one(t_cap)) : nullptr, a.take<sift_match>(m),
+          pairs ? a.take<float>(m * 2) : nullptr, pairs ? a.take<float>(m * 2) : nullptr, ratio_layout(a, blocks)};
+}
+
+// sift_bgr8_to_gray: the strided source rows, then the packed gray image.
+struct BgrHost { uint8_t* src; float* gray; };
+inline BgrHost bgr_host_layout(Carver& a, int rows, size_t row_stride, int out_rows, int out_cols) {
+  return {a.take<uint8_t>((size_t)rows * row_stride), a.take<float>((size_t)out_rows * out_cols)};
+}
+
+}  // namespace sift

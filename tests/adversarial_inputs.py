@@ -244,17 +244,19 @@ BATCH_ORDER = ["constant", "noise_u8", "constant", "stars", "constant"]  # empty
 # ---- the library's default capacities (read from its source, one truth) ---------
 def default_candidate_capacity(max_rows, max_cols):
     """Candidate slots per image of a fresh context: max(FLOOR, px / DIV) as
-    sift_ctx_create computes it (sift-gpu_amd/csrc/api.hip)."""
-    src = open(os.path.join(ROOT, "sift-gpu_amd", "csrc", "api.hip")).read()
-    m = re.search(r"per_img\s*=\s*std::max<long long>\((\d+),\s*px\s*/\s*(\d+)\)", src)
-    assert m, "sift_ctx_create no longer sizes the candidate workspace the way this helper reads"
-    return max(int(m.group(1)), max_rows * max_cols // int(m.group(2)))
+    sift_ctx_create computes it from the named constants of
+    sift-gpu_amd/csrc/ctx.hip."""
+    return max(_ctx_constant("kCandidateFloor"), max_rows * max_cols // _ctx_constant("kPixelsPerCandidate"))
 
 
 def keypoints_per_candidate_slot():
     """Initial internal keypoint buffer, in keypoints per candidate slot
-    (alloc_candidates in api.hip)."""
-    src = open(os.path.join(ROOT, "sift-gpu_amd", "csrc", "api.hip")).read()
-    m = re.search(r"ensure_kp\(c,\s*\(int\)std::min<long long>\(\(long long\)cap\s*\*\s*(\d+),", src)
-    assert m, "alloc_candidates no longer sizes the keypoint buffer the way this helper reads"
+    (alloc_candidates in ctx.hip)."""
+    return _ctx_constant("kKeypointsPerCandidateSlot")
+
+
+def _ctx_constant(name):
+    src = open(os.path.join(ROOT, "sift-gpu_amd", "csrc", "ctx.hip")).read()
+    m = re.search(r"constexpr\s+(?:long long|int)\s+" + name + r"\s*=\s*(\d+)\s*;", src)
+    assert m, f"ctx.hip no longer defines {name} the way this helper reads"
     return int(m.group(1))

@@ -92,6 +92,23 @@ def test_multi_gpu_host_compiles(tmp_path, siftgpu):
     assert build_multi_gpu_host(tmp_path / "multi_gpu").exists()
 
 
+def test_scratch_layouts(tmp_path):
+    """tests/cpp/scratch_layout.cpp: every scratch layout the matcher and
+    front-end entry points carve (csrc/scratch.hpp, plain host C++) at its
+    smallest and degenerate counts -- aligned, disjoint, inside the measured
+    total, both passes equal.  Built with the address and undefined-behaviour
+    sanitizers (their runtimes linked statically into the program) where the
+    host compiler has them, without otherwise."""
+    src = os.path.join(ROOT, "tests", "cpp", "scratch_layout.cpp")
+    exe = tmp_path / "scratch_layout"
+    base = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", src, "-o", str(exe)]
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"]
+    if subprocess.run(base + san, capture_output=True).returncode != 0:
+        subprocess.run(base, check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and "scratch layouts ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
 def test_ctx_create_fails_cleanly_without_gpu(siftgpu):
     import torch
     if torch.cuda.device_count() > 0:

@@ -257,6 +257,40 @@ def test_graph_cache_rotating_buffers(siftgpu, oracle):
     assert upd == caps - 1 == len(order) - 1, (caps, upd, inst)  # every other call patched it
 
 
+def test_graph_cache_evicts_first_in_first_out(siftgpu, oracle):
+    """The graph cache holds four entries and evicts the oldest capture; a hit
+    does not refresh an entry.  Five shapes on fixed buffers in the order
+    A B C D A E B A: A B C D miss, A hits, E evicts A, B hits, A misses --
+    6 captures and instantiations (an LRU cache would have kept A, evicted B
+    and counted 7).  Every call's output is the CPU path's."""
+    import torch
+    R0, C0 = 112, 144
+    shapes = {"A": (96, 128), "B": (96, 112), "C": (80, 128), "D": (112, 128), "E": (96, 144)}
+    ref = {s: oracle.sift(oracle.synth_image(70, r, c)) for s, (r, c) in shapes.items()}
+    assert all(len(k) > 0 for k, _ in ref.values()), {s: len(k) for s, (k, _) in ref.items()}
+    cap = 4 * max(len(k) for k, _ in ref.values())
+    with siftgpu.Context(R0, C0, 1, device=0) as ctx:
+        imgs = torch.empty((R0 * C0,), dtype=torch.float32, device="cuda")
+        kpts = torch.empty((cap, 7), dtype=torch.int32, device="cuda")
+        desc = torch.empty((cap, 128), dtype=torch.float32, device="cuda")
+        offs = torch.empty((2,), dtype=torch.int32, device="cuda")
+        before = ctx.graph_stats()
+        for s in "ABCDAEBA":
+            r, c = shapes[s]
+            ctx.synth_images(imgs.data_ptr(), 1, r, c, c, r * c, seed_base=70)
+            ctx.detect_compute_batch(imgs.data_ptr(), 1, r, c, c, r * c, kpts.data_ptr(), desc.data_ptr(), cap,
+                                     offs.data_ptr())
+            ctx.sync()
+            o = offs.cpu().numpy()
+            k, d = ref[s]
+            assert o[0] == 0 and o[1] == len(k), f"shape {s}"
+            assert_bits_equal(kpts[:o[1]].cpu().numpy().view(np.uint8).reshape(-1, 28), kp_bytes(k),
+                              f"shape {s} keypoints")
+            assert_bits_equal(desc[:o[1]].cpu().numpy(), d, f"shape {s} descriptors")
+        caps, upd, inst = (a - b for a, b in zip(ctx.graph_stats(), before))
+    assert (caps, inst, upd) == (6, 6, 0), (caps, upd, inst)
+
+
 def test_bench_plain_run_dumps_its_outputs(siftgpu, oracle, monkeypatch, capsys, tmp_path):
     """bench.py without --full, in this process, on a small batch split
     unevenly over its two streams (2 + 3 images): the line's headline fields,

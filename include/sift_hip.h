@@ -357,6 +357,38 @@ int sift_find_homography(const float* src_xy, const float* dst_xy, int n, double
                          double confidence, double* H, unsigned char* inlier_mask);
 int sift_perspective_transform(const double* H, const float* xy, int n, float* out_xy);
 
+/* The same for every segment of a batch, on the device in stream order: the
+ * last stage after sift_ratio_matches_device, whose outputs plug in unchanged.
+ * Segment b's pairs are rows [clamp(m_offsets[b]), clamp(m_offsets[b+1])) of
+ * d_src_xy / d_dst_xy, clamped to m_cap -- the ratio stage's convention
+ * (m_offsets[n_segments] may exceed m_cap).  Each segment gets exactly what
+ * sift_find_homography gives for its pairs, bit for bit: n < 4 none; n == 4 a
+ * direct fit with a mask of ones; else RANSAC, the refit on the inliers, 10 LM
+ * steps, normalisation.  d_H is [n_segments][9] row-major with H[8] = 1;
+ * d_found[b] is 1 for a model, 0 for none, and then H[b] is nine zeros and the
+ * segment's mask bytes are 0.  max_iters < 1 or confidence outside (0, 1) gives
+ * every segment found = 0.  d_inlier_mask is [m_cap] bytes by pair row and may
+ * be NULL; bytes outside [clamp(m_offsets[0]), clamp(m_offsets[n_segments]))
+ * are never written.
+ * Enqueued on the context stream, no synchronisation (the scratch grows, with
+ * a wait, only when a call needs more than any call before it).  n_segments
+ * == 0 or m_cap == 0: SIFT_OK, nothing enqueued.  A NULL context or a NULL
+ * required buffer: SIFT_E_INVALID (sift_last_error names it). */
+int sift_find_homography_segmented_device(sift_ctx* ctx, const float* d_src_xy, const float* d_dst_xy,
+                                          const int* d_m_offsets, int n_segments, int m_cap, double ransac_thresh,
+                                          int max_iters, double confidence, double* d_H, int* d_found,
+                                          unsigned char* d_inlier_mask /* may be NULL */);
+/* Host buffers (synchronous); src_xy / dst_xy have m_cap rows: */
+int sift_find_homography_segmented(sift_ctx* ctx, const float* src_xy, const float* dst_xy, const int* m_offsets,
+                                   int n_segments, int m_cap, double ransac_thresh, int max_iters, double confidence,
+                                   double* H, int* found, unsigned char* inlier_mask /* may be NULL */);
+/* d_out_xy[b][i] = perspectiveTransform(d_xy[i], H[b]) for the n_pts shared
+ * points (the object's corners), [n_segments][n_pts][2] floats; a segment with
+ * d_found[b] == 0 gets zeros.  Enqueued on the context stream, no
+ * synchronisation; n_segments == 0 or n_pts == 0: SIFT_OK, nothing enqueued. */
+int sift_perspective_transform_segmented_device(sift_ctx* ctx, const double* d_H, const int* d_found, int n_segments,
+                                                const float* d_xy, int n_pts, float* d_out_xy);
+
 /* ---- self-test ------------------------------------------------------------ */
 /* Evaluates one device arithmetic helper element-wise on host arrays (n
  * values), for bit-exact checks of the GPU math against the CPU oracle:

@@ -1,8 +1,9 @@
 // apps.hip -- the application stages behind the C ABI (include/sift_hip.h):
 // the L1 kNN matcher, its segmented form, the ratio test with point pairs and
-// the BGR8 front end, each in a device and a host form, and the homography
-// wrappers.  Host code only; the kernels live in match.hip, frontend.hip and
-// homography.hip.  Every form carves its scratch from the context's one block
+// the BGR8 front end, each in a device and a host form, the one-pair homography
+// wrappers and the segmented homography and corner transform.  Host code only;
+// the kernels live in match.hip, frontend.hip and homography_batch.hip (the
+// one-pair homography is host code in homography.hip).  Every form carves its scratch from the context's one block
 // by a layout of scratch.hpp.
 #include "ctx.hpp"
 #include "scratch.hpp"
@@ -104,6 +105,28 @@ int ratio_device(sift_ctx* c, const int* idx, const float* dist, const int* qoff
     StageScope sc(c, ST_RATIO, 0, 16.0 * q_cap);
     launch_ratio_matches(c->stream, idx, dist, qoff, n_segments, q_cap, ratio, q_kpts, t_kpts, toff, matches,
                          src_xy, dst_xy, m_cap, moff, blk_scan);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
+// ---- a whole batch: findHomography(RANSAC) per segment of the ratio stage's pairs (src/main.cpp:54-55) ----
+int check_homog(sift_ctx* c, const float* src_xy, const float* dst_xy, const int* m_offsets, int n_segments,
+                int m_cap, const double* H, const int* found) {
+  if (!c) return SIFT_E_INVALID;
+  if (n_segments < 0 || m_cap < 0) return fail(c, SIFT_E_INVALID, "negative count");
+  if (n_segments == 0 || m_cap == 0) return SIFT_OK;
+  if (!src_xy || !dst_xy || !m_offsets || !H || !found) return fail(c, SIFT_E_INVALID, "null buffer");
+  return SIFT_OK;
+}
+
+int homog_device(sift_ctx* c, const float* src_xy, const float* dst_xy, const int* moff, int n_segments, int m_cap,
+                 double thr, int max_iters, double confidence, double* H, int* found, unsigned char* mask_out,
+                 HomogParts P) {
+  {
+    StageScope sc(c, ST_HOMOG_SEG);  // the work depends on offsets and points only the device knows
+    launch_homography_seg(c->stream, src_xy, dst_xy, moff, n_segments, m_cap, thr, max_iters, confidence, P.subsets,
+                          P.models, P.counts, P.state, P.mask, H, found, mask_out);
   }
   HIP_TRY(c, hipGetLastError());
   return SIFT_OK;
@@ -311,6 +334,60 @@ int sift_find_homography(const float* src_xy, const float* dst_xy, int n, double
 int sift_perspective_transform(const double* H, const float* xy, int n, float* out_xy) {
   if (!H || n < 0 || (n > 0 && (!xy || !out_xy))) return SIFT_E_INVALID;
   perspective_transform(H, xy, n, out_xy);
+  return SIFT_OK;
+}
+
+// ---- the same for every segment of the ratio stage's point pairs, in stream order ----
+int sift_find_homography_segmented_device(sift_ctx* c, const float* d_src_xy, const float* d_dst_xy,
+                                          const int* d_m_offsets, int n_segments, int m_cap, double ransac_thresh,
+                                          int max_iters, double confidence, double* d_H, int* d_found,
+                                          unsigned char* d_inlier_mask) {
+  int rc = check_homog(c, d_src_xy, d_dst_xy, d_m_offsets, n_segments, m_cap, d_H, d_found);
+  if (rc || n_segments == 0 || m_cap == 0) return rc;
+  (void)hipSetDevice(c->device);
+  HomogParts P;
+  if ((rc = carve(c, &P, [&](Carver& a) { return homog_layout(a, n_segments, m_cap); }))) return rc;
+  return homog_device(c, d_src_xy, d_dst_xy, d_m_offsets, n_segments, m_cap, ransac_thresh, max_iters, confidence,
+                      d_H, d_found, d_inlier_mask, P);
+}
+
+int sift_find_homography_segmented(sift_ctx* c, const float* src_xy, const float* dst_xy, const int* m_offsets,
+                                   int n_segments, int m_cap, double ransac_thresh, int max_iters, double confidence,
+                                   double* H, int* found, unsigned char* inlier_mask) {
+  int rc = check_homog(c, src_xy, dst_xy, m_offsets, n_segments, m_cap, H, found);
+  if (rc || n_segments == 0 || m_cap == 0) return rc;
+  (void)hipSetDevice(c->device);
+  HomogHost S;
+  if ((rc = carve(c, &S, [&](Carver& a) { return homog_host_layout(a, n_segments, m_cap); }))) return rc;
+  const size_t xyb = (size_t)m_cap * 2 * sizeof(float), ob = (size_t)(n_segments + 1) * sizeof(int);
+  HIP_TRY(c, hipMemcpyAsync(S.src_xy, src_xy, xyb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.dst_xy, dst_xy, xyb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.m_off, m_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  if ((rc = homog_device(c, S.src_xy, S.dst_xy, S.m_off, n_segments, m_cap, ransac_thresh, max_iters, confidence, S.H,
+                         S.found, inlier_mask ? S.mask : nullptr, S.parts)))
+    return rc;
+  HIP_TRY(c, hipMemcpyAsync(H, S.H, (size_t)n_segments * 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(found, S.found, (size_t)n_segments * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  // only the segments' mask bytes come back: the others are left untouched, as in the device form
+  const int lo = clamp_off(m_offsets[0], m_cap), hi = clamp_off(m_offsets[n_segments], m_cap);
+  if (inlier_mask && hi > lo)
+    HIP_TRY(c, hipMemcpyAsync(inlier_mask + lo, S.mask + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SIFT_OK;
+}
+
+int sift_perspective_transform_segmented_device(sift_ctx* c, const double* d_H, const int* d_found, int n_segments,
+                                                const float* d_xy, int n_pts, float* d_out_xy) {
+  if (!c) return SIFT_E_INVALID;
+  if (n_segments < 0 || n_pts < 0) return fail(c, SIFT_E_INVALID, "negative count");
+  if (n_segments == 0 || n_pts == 0) return SIFT_OK;
+  if (!d_H || !d_found || !d_xy || !d_out_xy) return fail(c, SIFT_E_INVALID, "null buffer");
+  (void)hipSetDevice(c->device);
+  {
+    StageScope sc(c, ST_HOMOG_SEG, 0, 8.0 * n_pts * (n_segments + 1.0) + 76.0 * n_segments);
+    launch_perspective_seg(c->stream, d_H, d_found, n_segments, d_xy, n_pts, d_out_xy);
+  }
+  HIP_TRY(c, hipGetLastError());
   return SIFT_OK;
 }
 

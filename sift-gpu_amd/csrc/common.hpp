@@ -264,6 +264,15 @@ void launch_bgr8_gray(hipStream_t st, const uint8_t* src, long long sstride, lon
 int find_homography_ransac(const float* src_xy, const float* dst_xy, int n, double thr, int max_iters,
                            double confidence, double* H, unsigned char* mask_out);
 void perspective_transform(const double* H, const float* xy, int n, float* out);
+// Segmented forms (device-resident offsets, homography_batch.hip): one
+// workgroup per segment; the scratch pieces are scratch.hpp's HomogParts.
+struct HomogState;
+void launch_homography_seg(hipStream_t st, const float* src_xy, const float* dst_xy, const int* moff, int n_segments,
+                           int m_cap, double thr, int max_iters, double confidence, int* subsets, double* models,
+                           int* counts, HomogState* state, unsigned char* mask, double* H, int* found,
+                           unsigned char* mask_out);
+void launch_perspective_seg(hipStream_t st, const double* H, const int* found, int n_segments, const float* xy,
+                            int n_pts, float* out);
 int knn_splits(int nq, int nt);
 void launch_knn_l1(hipStream_t st, const float* q, int nq, const float* t, int nt, int k, int splits,
                    float2* part_d, int2* part_i, int* idx, float* dist);

@@ -1,8 +1,9 @@
-// scratch.hpp -- how the matcher and front-end entry points divide the
-// context's one scratch block (sift_ctx::d_match).  Each layout is described
-// once, as a function of a Carver, and run twice: on a null base to measure the
-// block, then on the block itself.  Plain host C++ (no HIP include), so that
-// tests/cpp/scratch_layout.cpp checks every layout without a GPU.
+// scratch.hpp -- how the matcher, front-end and segmented-homography entry
+// points divide the context's one scratch block (sift_ctx::d_match).  Each
+// layout is described once, as a function of a Carver, and run twice: on a null
+// base to measure the block, then on the block itself.  Plain host C++ (no HIP
+// include), so that tests/cpp/scratch_layout.cpp and homography_layout.cpp
+// check every layout without a GPU.
 #pragma once
 
 #include <stddef.h>
@@ -106,6 +107,30 @@ inline RatioHost ratio_host_layout(Carver& a, int n_segments, int q_cap, int t_c
 struct BgrHost { uint8_t* src; float* gray; };
 inline BgrHost bgr_host_layout(Carver& a, int rows, size_t row_stride, int out_rows, int out_cols) {
   return {a.take<uint8_t>((size_t)rows * row_stride), a.take<float>((size_t)out_rows * out_cols)};
+}
+
+// sift_find_homography_segmented_device (homography_batch.hip): per segment one
+// round of kHomogRound hypotheses -- the accepted 4-point subsets, their models
+// and inlier counts (-1: no model) -- then the state the RANSAC kernel hands to
+// the refinement kernel, and the best hypothesis's inlier mask by pair row.
+constexpr int kHomogRound = 64;
+struct HomogState { double best[9]; int found, max_good; };
+struct HomogParts { int* subsets; double* models; int* counts; HomogState* state; unsigned char* mask; };
+inline HomogParts homog_layout(Carver& a, int n_segments, int m_cap) {
+  const size_t jobs = (size_t)n_segments * kHomogRound;
+  return {a.take<int>(jobs * 4), a.take<double>(jobs * 9), a.take<int>(jobs), a.take<HomogState>((size_t)n_segments),
+          a.take<unsigned char>((size_t)m_cap)};
+}
+
+// sift_find_homography_segmented: the staged point pairs and offsets, the
+// staged results, then the device form's pieces.
+struct HomogHost {
+  float *src_xy, *dst_xy; int* m_off; double* H; int* found; unsigned char* mask; HomogParts parts;
+};
+inline HomogHost homog_host_layout(Carver& a, int n_segments, int m_cap) {
+  return {a.take<float>((size_t)m_cap * 2), a.take<float>((size_t)m_cap * 2), a.take<int>((size_t)n_segments + 1),
+          a.take<double>((size_t)n_segments * 9), a.take<int>((size_t)n_segments),
+          a.take<unsigned char>((size_t)m_cap), homog_layout(a, n_segments, m_cap)};
 }
 
 }  // namespace sift

@@ -36,6 +36,7 @@ SIFT_MULTI_SELF_P2P = 0x100  # sift_multi_create: device 0's own records over RC
 SIFT_E_WORKSPACE = -6  # internal candidate workspace overflow: an error, never the sizing case
 SIFT_FLAG_FAST, SIFT_FLAG_PROFILE, SIFT_FLAG_VERBOSE, SIFT_FLAG_NO_GRAPH = 0x1, 0x2, 0x4, 0x8
 N_SCALES, N_DOG, DESC_LEN = 5, 4, 128
+HOMOGRAPHY_ROUND = 64  # hypotheses per round of the segmented homography (scratch.hpp kHomogRound)
 
 KEYPOINT_DTYPE = np.dtype(
     [("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
@@ -117,6 +118,11 @@ def lib():
                                                vp]),
             "sift_ratio_matches": (ip, [vp, pint, fp, pint, ip, ip, ctypes.c_double, vp, vp, ip, pint, vp, fp, fp,
                                         ip, pint]),
+            "sift_find_homography_segmented_device": (ip, [vp, vp, vp, vp, ip, ip, ctypes.c_double, ip,
+                                                           ctypes.c_double, vp, vp, vp]),
+            "sift_find_homography_segmented": (ip, [vp, fp, fp, pint, ip, ip, ctypes.c_double, ip, ctypes.c_double,
+                                                    ctypes.POINTER(ctypes.c_double), pint, vp]),
+            "sift_perspective_transform_segmented_device": (ip, [vp, vp, vp, ip, vp, ip, vp]),
             "sift_multi_shard": (ip, [ip, ip, ip, pint, pint]),
             "sift_multi_merge_offsets": (ip, [ctypes.POINTER(pint), pint, ip, pint]),
             "sift_multi_create": (ip, [pint, ip, ip, ip, ip, ctypes.c_uint, ip, ip, ip, ctypes.POINTER(vp)]),
@@ -453,6 +459,55 @@ class Context:
                         n, moff.ctypes.data_as(pint)))
         m = int(moff[-1])
         return matches[:m], moff, (None if src is None else src[:m]), (None if dst is None else dst[:m])
+
+    # ---- a whole batch: homography per segment of the ratio stage's pairs ---
+    def find_homography_segmented_device(self, src_xy_ptr: int, dst_xy_ptr: int, m_offsets_ptr: int,
+                                         n_segments: int, m_cap: int, H_ptr: int, found_ptr: int,
+                                         mask_ptr: int | None = None, ransacReprojThreshold: float = 3.0,
+                                         maxIters: int = 2000, confidence: float = 0.995):
+        """Device-pointer form (no sync) of findHomography(RANSAC) for every
+        segment [m_offsets[b], m_offsets[b+1]) of ratio_matches_device's point
+        pairs: H_ptr [n_segments][9] float64, found_ptr [n_segments] int32,
+        mask_ptr [m_cap] uint8 or None."""
+        vp = lambda p: ctypes.c_void_p(p or None)  # noqa: E731
+        self._check("sift_find_homography_segmented_device",
+                    self._L.sift_find_homography_segmented_device(
+                        self.h, vp(src_xy_ptr), vp(dst_xy_ptr), vp(m_offsets_ptr), n_segments, m_cap,
+                        float(ransacReprojThreshold), int(maxIters), float(confidence), vp(H_ptr), vp(found_ptr),
+                        vp(mask_ptr)))
+
+    def perspective_transform_segmented_device(self, H_ptr: int, found_ptr: int, n_segments: int, xy_ptr: int,
+                                               n_pts: int, out_xy_ptr: int):
+        """Device-pointer form (no sync): out[b][i] = perspectiveTransform(xy[i], H[b]),
+        zeros where found[b] == 0; out_xy_ptr is [n_segments][n_pts][2] float32."""
+        vp = lambda p: ctypes.c_void_p(p or None)  # noqa: E731
+        self._check("sift_perspective_transform_segmented_device",
+                    self._L.sift_perspective_transform_segmented_device(self.h, vp(H_ptr), vp(found_ptr), n_segments,
+                                                                        vp(xy_ptr), n_pts, vp(out_xy_ptr)))
+
+    def findHomographyBatch(self, src, dst, m_offsets, ransacReprojThreshold: float = 3.0, maxIters: int = 2000,
+                            confidence: float = 0.995):
+        """findHomography(RANSAC) for every segment at once (host arrays): a list
+        of (H 3x3 float64 or None, inlier mask uint8[segment's pairs]) per
+        segment, offsets clamped to the number of pairs."""
+        s = np.ascontiguousarray(src, np.float32).reshape(-1, 2)
+        d = np.ascontiguousarray(dst, np.float32).reshape(-1, 2)
+        mo = np.ascontiguousarray(m_offsets, np.int32)
+        if len(s) != len(d) or mo.ndim != 1 or len(mo) < 1:
+            raise ValueError("src / dst must be [n, 2] and m_offsets n_segments + 1 entries")
+        nseg, n = len(mo) - 1, len(s)
+        H = np.zeros((nseg, 9), np.float64)
+        found = np.zeros(nseg, np.int32)
+        mask = np.zeros(n, np.uint8)
+        pint = ctypes.POINTER(ctypes.c_int)
+        self._check("sift_find_homography_segmented",
+                    self._L.sift_find_homography_segmented(
+                        self.h, _fp(s), _fp(d), mo.ctypes.data_as(pint), nseg, n, float(ransacReprojThreshold),
+                        int(maxIters), float(confidence), H.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                        found.ctypes.data_as(pint), mask.ctypes.data))
+        o = np.clip(mo.astype(np.int64), 0, n)
+        return [(H[b].reshape(3, 3).copy() if found[b] else None, mask[o[b]:max(o[b], o[b + 1])].copy())
+                for b in range(nseg)]
 
     # ---- device batch API ------------------------------------------------
     def synth_images(self, out_ptr: int, batch: int, rows: int, cols: int, row_stride: int,

@@ -352,7 +352,20 @@ int sift_ratio_matches(sift_ctx* ctx, const int* idx, const float* dist, const i
  * Levenberg-Marquardt on H[0..7] (normal equations, Gaussian elimination), not
  * OpenCV's LMSolver, so H can differ from cv::findHomography's in the last
  * digits (the RANSAC sampling and inlier mask follow OpenCV's order).  Parity
- * is pinned only against oracle/homography.py, which restates the same steps. */
+ * is pinned only against oracle/homography.py, which restates the same steps.
+ * n == 4 is a direct fit with no subset check (OpenCV's rule): a degenerate
+ * quadruple gives none where a coordinate has no spread (four identical pairs,
+ * a common dst point, a common x), and otherwise a model that may be finite but
+ * meaningless (four collinear pairs: entries near 1e15).
+ * A pair is an inlier iff its float reprojection error is <= (float)(thr * thr):
+ * thr = -3 behaves as 3, thr = 0 admits only an exact zero error, and a thr
+ * whose square overflows float to +inf admits every pair with a finite or
+ * infinite (not NaN) error, so the first hypothesis ends the loop.
+ * Non-finite coordinates: the call terminates (every loop is bounded by a
+ * count), a row with a NaN coordinate or an infinite src coordinate is never an
+ * inlier, one with an infinite dst coordinate only under the +inf limit above;
+ * what the pair set as a whole gives (found, H) is otherwise unspecified.  In
+ * the segmented forms below the other segments are unaffected. */
 int sift_find_homography(const float* src_xy, const float* dst_xy, int n, double ransac_thresh, int max_iters,
                          double confidence, double* H, unsigned char* inlier_mask);
 int sift_perspective_transform(const double* H, const float* xy, int n, float* out_xy);
@@ -394,7 +407,11 @@ int sift_perspective_transform_segmented_device(sift_ctx* ctx, const double* d_H
  * values), for bit-exact checks of the GPU math against the CPU oracle:
  * op 0 exp32f(a), 1 fastAtan2(a, b) (y = a, x = b, degrees), 2 magnitude(a, b),
  * 3 (float)cos((double)a), 4 (float)sin((double)a), 5 (float)exp2((double)a),
- * 6 cvRound(a) (as float), 7 cvFloor(a) (as float). */
+ * 6 cvRound(a) (as float), 7 cvFloor(a) (as float),
+ * 8 the homography's RANSACUpdateNumIters(0.995, (double)(b - a) / b, 4, 2000)
+ * for a = good inliers of b = n pairs (integers as floats, exact below 2^24; the
+ * result as float), 9 the same with confidence 0.5: the one libm-dependent
+ * site of sift_find_homography_segmented_device, evaluated on the device. */
 int sift_selftest_math(sift_ctx* ctx, int op, const float* a, const float* b, float* out, int n);
 
 /* ---- profiling ------------------------------------------------------------ */

@@ -273,6 +273,9 @@ void launch_homography_seg(hipStream_t st, const float* src_xy, const float* dst
                            unsigned char* mask_out);
 void launch_perspective_seg(hipStream_t st, const double* H, const int* found, int n_segments, const float* xy,
                             int n_pts, float* out);
+// sift_selftest_math ops 8 / 9: out[i] = update_num_iters(confidence, (good[i] of n[i] pairs), 4, 2000)
+void launch_update_num_iters_selftest(hipStream_t st, double confidence, const float* good, const float* n, float* out,
+                                      int count);
 int knn_splits(int nq, int nt);
 void launch_knn_l1(hipStream_t st, const float* q, int nq, const float* t, int nt, int k, int splits,
                    float2* part_d, int2* part_i, int* idx, float* dist);

@@ -329,7 +329,22 @@ __global__ void perspective_seg_kernel(const double* __restrict__ H, const int* 
   out[2 * g + 1] = o[1];
 }
 
+// The libm-dependent site on the device's own pow / log (sift_selftest_math ops 8, 9).
+__global__ __launch_bounds__(256) void update_num_iters_selftest_kernel(double confidence, const float* __restrict__ good,
+                                                                         const float* __restrict__ n,
+                                                                         float* __restrict__ out, int count) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const int g = (int)good[i], m = (int)n[i];
+  out[i] = (float)update_num_iters(confidence, (double)(m - g) / m, 4, 2000);
+}
+
 }  // namespace
+
+void launch_update_num_iters_selftest(hipStream_t st, double confidence, const float* good, const float* n, float* out,
+                                      int count) {
+  update_num_iters_selftest_kernel<<<(count + 255) / 256, 256, 0, st>>>(confidence, good, n, out, count);
+}
 
 void launch_homography_seg(hipStream_t st, const float* src_xy, const float* dst_xy, const int* moff, int n_segments,
                            int m_cap, double thr, int max_iters, double confidence, int* subsets, double* models,

@@ -471,7 +471,7 @@ int sift_calc_descriptors(sift_ctx* c, const float* gpyr, int rows, int cols, in
 
 int sift_selftest_math(sift_ctx* c, int op, const float* a, const float* b, float* out, int n) {
   if (!c) return SIFT_E_INVALID;
-  if (!a || !out || n < 0 || op < 0 || op > 7 || ((op == 1 || op == 2) && !b))
+  if (!a || !out || n < 0 || op < 0 || op > 9 || ((op == 1 || op == 2 || op >= 8) && !b))
     return fail(c, SIFT_E_INVALID, "bad selftest arguments");
   if (n == 0) return SIFT_OK;
   (void)hipSetDevice(c->device);
@@ -482,7 +482,10 @@ int sift_selftest_math(sift_ctx* c, int op, const float* a, const float* b, floa
   hipError_t e = hipMemcpy(da, a, sizeof(float) * n, hipMemcpyHostToDevice);
   if (e == hipSuccess && b) e = hipMemcpy(db, b, sizeof(float) * n, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    launch_math_selftest(c->stream, op, da, db, dout, n, c->d_mc);
+    if (op >= 8)
+      launch_update_num_iters_selftest(c->stream, op == 8 ? 0.995 : 0.5, da, db, dout, n);
+    else
+      launch_math_selftest(c->stream, op, da, db, dout, n, c->d_mc);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);

@@ -525,6 +525,9 @@ class Context:
                                                       ctypes.c_void_p(offs_ptr)))
 
     def selftest_math(self, op: int, a: np.ndarray, b: np.ndarray | None = None) -> np.ndarray:
+        """One device helper element-wise (sift_hip.h lists ops 0..7); ops 8 / 9 are the
+        homography's update_num_iters(0.995 / 0.5, (b - a) / b, 4, 2000) for a = good
+        inliers of b = n pairs, integers as float32, the result as float32."""
         a = np.ascontiguousarray(a, np.float32)
         bb = np.ascontiguousarray(b if b is not None else a, np.float32)
         out = np.empty_like(a)

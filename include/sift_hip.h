@@ -413,6 +413,12 @@ int sift_perspective_transform_segmented_device(sift_ctx* ctx, const double* d_H
  * result as float), 9 the same with confidence 0.5: the one libm-dependent
  * site of sift_find_homography_segmented_device, evaluated on the device. */
 int sift_selftest_math(sift_ctx* ctx, int op, const float* a, const float* b, float* out, int n);
+/* The point evaluation of an octave's widest scale that batch SIFT_NCL uses
+ * instead of blurring that plane: for each of n points (r, c) = rc[2i], rc[2i+1]
+ * of a packed rows x cols plane, out[9i + 3(dy+1) + (dx+1)] =
+ * Gaussian_Blur(plane, sig[4]) at (r + dy, c + dx), dy, dx in -1..1 -- the dense
+ * blur's floats.  Points may lie anywhere with |r|, |c| < 2^20. */
+int sift_selftest_g4_points(sift_ctx* ctx, const float* plane, int rows, int cols, const int* rc, int n, float* out);
 
 /* ---- profiling ------------------------------------------------------------ */
 /* With SIFT_FLAG_PROFILE: per-stage device time accumulated since the last

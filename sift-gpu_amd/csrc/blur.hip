@@ -680,6 +680,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void bl
   }
 }
 
+// The same launch without plane 4 (SIFT_NCL's sparse flow: detection takes
+// the widest scale point by point, detect.hip's g4_fill_kernel): slot s blurs
+// scale 3 - s.  Its own kernel, so that no w = 18 walk is instantiated: the
+// walks left need 70 VGPRs.  The register hold keeps the 3 waves per SIMD of
+// the four-slot kernel on purpose -- the finding above is about the
+// neighbouring stream, and it holds for the shorter kernel too: bench.py's
+// two-stream step 15.09-15.24 ms held, 15.82-16.10 ms at 70 VGPRs (7 waves
+// per SIMD); profiles/sparse_g4_ab.txt.  Chunk rule cp = 0.7 re-measured with
+// three slots: 0.5 15.29-15.40 ms, 0.7 15.09-15.24, 1.0 15.15-15.21.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void blur_sym3_kernel(SymArgs A) {
+  __shared__ float ring[kSymRing];
+  asm volatile("; hold v160-v167" ::: "v160", "v167");
+  const int wid = blockIdx.x;
+  const int slot = wid >= A.start[2] ? 2 : wid >= A.start[1] ? 1 : 0;
+  const int local = sym_local(A, slot, wid);
+  if (local < 0) return;
+  switch (slot) {
+    case 0: sym_walk<3>(A, 0, local, ring); break;
+    case 1: sym_walk<2>(A, 1, local, ring); break;
+    default: sym_walk<1>(A, 2, local, ring); break;
+  }
+}
+
 // The octave-0 base (createInitialImage's blur of the input, table 0).
 __global__ __launch_bounds__(64) void blur_sym_base_kernel(SymArgs A) {
   __shared__ float ring[SymSeg<kSymW0>::RING];
@@ -776,7 +799,8 @@ void launch_blur_base_sym(hipStream_t st, Plane src, float* dst, long long dpitc
   hipLaunchKernelGGL(blur_sym_base_kernel, dim3(A.start[1]), dim3(64), 0, st, A);
 }
 
-void launch_blur_octave_sym(hipStream_t st, const Layout& L, int o, float* gpyr, int batch, bool fuse_next) {
+void launch_blur_octave_sym(hipStream_t st, const Layout& L, int o, float* gpyr, int batch, bool fuse_next,
+                            bool no_plane4) {
   const Octave& O = L.oct[o];
   SymArgs A{};
   const NextPlane nx = next_plane(L, o, gpyr, fuse_next);
@@ -785,7 +809,8 @@ void launch_blur_octave_sym(hipStream_t st, const Layout& L, int o, float* gpyr,
   A.src = gpyr + O.g_off[0];
   A.s_pitch = O.pitch;
   A.s_img = L.g_img;
-  for (int s = 0; s < 4; ++s) A.dst[s] = gpyr + O.g_off[4 - s];
+  const int first = no_plane4 ? 3 : 4;  // slot s blurs scale first - s
+  for (int s = 0; s < first; ++s) A.dst[s] = gpyr + O.g_off[first - s];
   A.d_pitch = O.pitch;
   A.d_img = L.g_img;
   A.rows = O.rows;
@@ -793,8 +818,13 @@ void launch_blur_octave_sym(hipStream_t st, const Layout& L, int o, float* gpyr,
   A.strips = (O.cols + 63) / 64;
   A.batch = batch;
   const int w[4] = {kSymW4, kSymW3, kSymW2, kSymW1};
-  sym_plan(A, w, 4, 0.7);
-  hipLaunchKernelGGL(blur_sym_kernel, dim3(A.start[4]), dim3(64), 0, st, A);
+  if (no_plane4) {
+    sym_plan(A, w + 1, 3, 0.7);  // re-measured with three slots (profiles/sparse_g4_ab.txt)
+    hipLaunchKernelGGL(blur_sym3_kernel, dim3(A.start[3]), dim3(64), 0, st, A);
+  } else {
+    sym_plan(A, w, 4, 0.7);
+    hipLaunchKernelGGL(blur_sym_kernel, dim3(A.start[4]), dim3(64), 0, st, A);
+  }
 }
 
 // ---- resize INTER_NEAREST to the next octave (src/sift.cpp:252-254) -------

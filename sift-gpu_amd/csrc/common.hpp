@@ -251,7 +251,10 @@ long long blur_octave_tiles(const Layout& L, int o, int batch);
 bool sym_tables_match(const float* coefs);
 void launch_blur_base_sym(hipStream_t st, Plane src, float* dst, long long dpitch, long long dimg, int rows,
                           int cols, int batch);
-void launch_blur_octave_sym(hipStream_t st, const Layout& L, int o, float* gpyr, int batch, bool fuse_next);
+// no_plane4: planes 1..3 only (three slots, chunks sized from w = 12); plane 4
+// keeps whatever it held.
+void launch_blur_octave_sym(hipStream_t st, const Layout& L, int o, float* gpyr, int batch, bool fuse_next,
+                            bool no_plane4 = false);
 void launch_decimate(hipStream_t st, const Layout& L, int o, float* gpyr, int batch);
 void launch_dog(hipStream_t st, const Layout& L, int o, const float* gpyr, float* dog, int batch);
 void launch_blur_1d(hipStream_t st, int w, const float* coef1d, Plane src, float* tmp, float* dst,
@@ -337,16 +340,35 @@ struct DetectBufs {
   int* npeaks;          // orientation peaks per candidate, [cand_cap]
   int* scan_tmp;        // exclusive scan of blk_counts, [blk_cap+1]
   int* scan_tiles;      // per-tile sums of the multi-block scan, [scan_tiles_for(max(blk_cap, cand_cap))]
+  float* g4patch;       // sparse flow: plane 4 on the 3x3 around the slot's current (r, c), [9 * cand_cap]
+  int* rstate;          // sparse flow: Newton iteration a slot waits at for its patch, or -1 (done), [cand_cap]
+};
+// The sparse flow of SIFT_NCL's detection (exact mode, batches): bit o of
+// `sparse` marks an octave whose plane 4 was not blurred.  There the extrema
+// pass tests layer 2 against DoG 1 and DoG 2 only ("partial candidates"), and
+// plane 4 is evaluated point by point -- the reference's 37 x 37 chain,
+// g4_fill_kernel -- on the 3x3 around each candidate that sits on layer 2:
+// once for the nine DoG 3 comparisons left out, then again whenever a Newton
+// step moves a candidate on layer 2 (at most kMaxInterp rounds of fill + step).
+// coef4 is the context's table of sig[4] (37 x 37, row-major).
+struct SparseG4 {
+  unsigned sparse;
+  const float* coef4;
 };
 int scan_tiles_for(long long cap);
 long long mask_words_per_image(const Layout& L);
 int mask_blocks_per_image(const Layout& L);
 void launch_extrema(hipStream_t st, const Layout& L, const float* gpyr, float* dog, bool write_dog,
-                    float2* grad, const MathConsts* mc, int batch, DetectBufs& D);
+                    float2* grad, const MathConsts* mc, int batch, DetectBufs& D, unsigned sparse = 0);
 void launch_grad(hipStream_t st, const Layout& L, const float* gpyr, float2* grad, int batch, int s_lo,
                  int s_hi, const MathConsts* mc);
 void launch_refine_orient(hipStream_t st, const Layout& L, const float* gpyr, const float2* grad,
-                          const float* dog, const MathConsts* mc, DetectBufs& D, int batch);
+                          const float* dog, const MathConsts* mc, DetectBufs& D, int batch,
+                          SparseG4 sp = SparseG4{0, nullptr});
+// Test entry (sift_selftest_g4_points): plane 4's 3x3 patch around each of n
+// points of a one-octave layout whose plane 0 holds the source.
+void launch_g4_points(hipStream_t st, const Layout& L, const float* gpyr, const float* coef4, const Cand* pts, int n,
+                      const int* n_dev, float* patch);
 void launch_emit(hipStream_t st, DetectBufs& D, int batch, sift_keypoint* kpts, int kp_cap,
                  int* img_kp_off);
 // Device status bits; bit i <-> sticky error word err[i] (DescArgs::err_flag = &err[0],

@@ -173,9 +173,11 @@ int alloc_candidates(sift_ctx* c, int cap) {
   const bool ok = c->cands.grow((size_t)cap) == hipSuccess && c->couts.grow((size_t)cap) == hipSuccess &&
                   c->kp_scan.grow((size_t)cap + 1) == hipSuccess && c->npeaks.grow((size_t)cap) == hipSuccess &&
                   c->scan_tmp.grow(scan_n) == hipSuccess &&
-                  c->scan_tiles.grow((size_t)scan_tiles_for((long long)scan_n) + 1) == hipSuccess;
+                  c->scan_tiles.grow((size_t)scan_tiles_for((long long)scan_n) + 1) == hipSuccess &&
+                  c->g4patch.grow((size_t)cap * 9) == hipSuccess && c->rstate.grow((size_t)cap) == hipSuccess;
   c->D = DetectBufs{c->mask,    c->blk_counts, c->cand_total, c->img_cand_off, c->cands,    ok ? cap : 0,
-                    c->couts,   c->kp_scan,    c->kp_total,   c->npeaks,       c->scan_tmp, c->scan_tiles};
+                    c->couts,   c->kp_scan,    c->kp_total,   c->npeaks,       c->scan_tmp, c->scan_tiles,
+                    c->g4patch, c->rstate};
   if (!ok) return fail(c, SIFT_E_NOMEM, "candidate workspace allocation failed");
   return ensure_kp(c, (int)std::min<long long>((long long)cap * kKeypointsPerCandidateSlot, 1 << 28));
 }
@@ -352,6 +354,10 @@ int sift_ctx_create(int device, int max_rows, int max_cols, int max_batch, unsig
     if (r) c->sym_rows = atoi(r);
     const char* sm = getenv("SIFT_HIP_SMALL_MAX");
     if (sm) c->small_max = atoll(sm);
+    // the sparse flow's point evaluation reads sig[4]'s table from d_coef,
+    // which sym_tables_match ties to the scatter blur's literals
+    const char* dg = getenv("SIFT_HIP_DENSE_G4");
+    c->sparse_g4 = c->sym_blur && !(dg && atoi(dg) != 0);
   }
   // SIFT_FLAG_FAST: pyramid_pc.hip carries its 1-D taps as literals; a
   // mismatch with the host formula makes the flag an error (enqueue-time check)

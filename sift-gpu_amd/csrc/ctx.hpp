@@ -100,6 +100,9 @@ struct sift_ctx {
   bool sym_blur = false;          // symmetric scatter blur (blur.hip) for the base and octave scales
   int sym_min = 256;              // ... for launches of >= sym_min 64-column strips x images
   int sym_rows = 0;               //     of >= sym_rows rows (A/B knob, SIFT_HIP_SYM_ROWS_MIN)
+  // SIFT_NCL on a batch, exact mode: octaves on the scatter blur skip plane 4
+  // and detection evaluates it point by point (SIFT_HIP_DENSE_G4=1: off, A/B)
+  bool sparse_g4 = false;
   size_t coef_base_off = 0, coef_oct_off = 0;
   sift::Buf<sift::MathConsts> d_mc;
   // detection workspace: the owners, and the raw-pointer view of them that the
@@ -108,6 +111,8 @@ struct sift_ctx {
   sift::Buf<int> blk_counts, cand_total, img_cand_off, kp_scan, kp_total, npeaks, scan_tmp, scan_tiles;
   sift::Buf<sift::Cand> cands;
   sift::Buf<sift::CandOut> couts;
+  sift::Buf<float> g4patch;       // sparse flow (SparseG4, common.hpp): 9 floats per candidate slot
+  sift::Buf<int> rstate;          //   and the slot's waiting state
   sift::DetectBufs D{};
   int blk_cap = 0;
   sift::Buf<int> d_img_off;       // [max_batch+1] for the host entry points

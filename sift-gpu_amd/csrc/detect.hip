@@ -106,6 +106,7 @@ struct WalkArgs {
   int wave_start[kMaxOctaves + 1];  // first wave (blockIdx.x) of octave o
   int strips[kMaxOctaves];
   int chunk;                        // rows per wave
+  unsigned sparse;                  // bit o: octave o has no plane 4 (FROM_G only): layer 2 is tested without DoG 3
 };
 
 // src/sift.cpp:493-511 at ring column c: lo/cu/hi[k] = row y - 1 + k of the
@@ -159,6 +160,10 @@ __global__ __launch_bounds__(64) void extrema_walk_kernel(WalkArgs A) {
   const long long pitch = O.pitch;
   const float* g = A.gpyr + b * A.L.g_img;
   const float* dg = FROM_G ? nullptr : A.dog + b * A.L.d_img;
+  // no plane 4 in this octave (uniform): it is not loaded, DoG 3 is not formed
+  // and layer 2 passes on its other 17 neighbours (a partial candidate; the
+  // nine DoG 3 comparisons follow in refine_step_kernel<true>)
+  const bool sp = FROM_G && ((A.sparse >> o) & 1u);
   const int xm = x0 + lane;                       // this lane's column
   const int xh = lane == 0 ? x0 - 1 : x0 + 64;    // halo column of lanes 0, 1
   const bool hl = lane < 2;
@@ -173,7 +178,7 @@ __global__ __launch_bounds__(64) void extrema_walk_kernel(WalkArgs A) {
     if (FROM_G) {
       v[2] = g[O.g_off[0] + pm];
       v[3] = g[O.g_off[3] + pm];
-      v[4] = g[O.g_off[4] + pm];
+      v[4] = sp ? 0.f : g[O.g_off[4] + pm];
     } else {
 #pragma unroll
       for (int k = 0; k < kDogPer; ++k) v[2 + k] = dg[O.d_off[k] + pm];
@@ -184,7 +189,7 @@ __global__ __launch_bounds__(64) void extrema_walk_kernel(WalkArgs A) {
       if (FROM_G) {
         h[2] = g[O.g_off[0] + ph];
         h[3] = g[O.g_off[3] + ph];
-        h[4] = g[O.g_off[4] + ph];
+        h[4] = sp ? 0.f : g[O.g_off[4] + ph];
       } else {
 #pragma unroll
         for (int k = 0; k < kDogPer; ++k) h[2 + k] = dg[O.d_off[k] + ph];
@@ -271,8 +276,11 @@ __global__ __launch_bounds__(64) void extrema_walk_kernel(WalkArgs A) {
 #pragma unroll
     for (int l = 0; l < 2; ++l) {
       const float v = od[sm][1 + l];
-      const float nmax = fmaxf(fmaxf(mx9[l], mx8[l]), mx9[l + 2]);
-      const float nmin = fminf(fminf(mn9[l], mn8[l]), mn9[l + 2]);
+      float nmax = fmaxf(mx9[l], mx8[l]), nmin = fminf(mn9[l], mn8[l]);
+      if (!(sp && l == 1)) {
+        nmax = fmaxf(nmax, mx9[l + 2]);
+        nmin = fminf(nmin, mn9[l + 2]);
+      }
       f[l] = inside && fabsf(v) > kDogThreshold && ((v > 0 && v >= nmax) || (v < 0 && v <= nmin));
     }
     const unsigned long long m1 = __ballot(f[0]), m2 = __ballot(f[1]);
@@ -639,8 +647,9 @@ void launch_grad(hipStream_t st, const Layout& L, const float* gpyr, float2* gra
 }
 
 void launch_extrema(hipStream_t st, const Layout& L, const float* gpyr, float* dog, bool write_dog,
-                    float2* grad, const MathConsts* mc, int batch, DetectBufs& D) {
+                    float2* grad, const MathConsts* mc, int batch, DetectBufs& D, unsigned sparse) {
   WalkArgs W;
+  W.sparse = write_dog ? sparse : 0u;
   W.L = L;
   W.M = make_mask(L);
   W.gpyr = gpyr;
@@ -693,11 +702,18 @@ struct RefArgs {
   int cand_cap;
   CandOut* couts;
   int* npeaks;
+  // sparse flow (SparseG4 in common.hpp); sparse == 0: the dense flow
+  unsigned sparse;
+  const float* coef4;
+  float* patch;
+  int* rstate;
 };
 
 // adjustLocalExtrema (src/sift.cpp:287-388) for one candidate.
 struct Refined {
   bool ok;
+  bool pending;  // SPARSE: stopped before iteration `it` at (layer 2, r, c), whose patch is not filled yet
+  int it;
   int layer, r, c, octave;
   float x, y, size, response;
 };
@@ -705,10 +721,19 @@ struct Refined {
 // DoG value of layer l at (yy, xx): the stored DoG plane, or -- FROM_G -- the
 // difference of the Gaussian planes l+1 and l that buildDoGPyramid stores
 // (src/sift.cpp:276; the same float subtraction, so bit-identical).
-template <bool FROM_G>
+//
+// SPARSE (FROM_G; the octave has no plane 4): the walk starts at iteration it0
+// and takes plane 4 from `patch` -- its 3x3 around (pr, pc), g4_fill_kernel's
+// floats, the plane's own bit for bit -- whenever the cube reaches it, i.e. on
+// layer 2.  On layer 2 at any other position it returns `pending` with its
+// state before that iteration; the caller has the patch filled there and
+// calls again.  The arithmetic is the same term for term.
+template <bool FROM_G, bool SPARSE = false>
 __device__ __forceinline__ Refined refine_candidate(const Layout& Lay, const float* __restrict__ dimg,
                                                     const float* __restrict__ gimg, int o, int layer, int r,
-                                                    int c) {
+                                                    int c, int it0 = 0, const float* __restrict__ patch = nullptr,
+                                                    int pr = -1, int pc = -1) {
+  static_assert(FROM_G || !SPARSE, "the sparse flow forms DoG from the Gaussian planes");
   const Octave& O = Lay.oct[o];
   const long long pitch = O.pitch;
   const float img_scale = 1. / 255;
@@ -718,7 +743,7 @@ __device__ __forceinline__ Refined refine_candidate(const Layout& Lay, const flo
   float xi = 0, xr = 0, xc = 0, contr = 0;
   Refined R{};
   R.ok = true;
-  int it = 0;
+  int it = it0;
   // The 3x3 neighbourhood of (r, c) in DoG layers layer-1 .. layer+1, loaded
   // once per Newton step as one 12-byte row per plane and row (FROM_G: four
   // Gaussian planes, DoG = g[l+1] - g[l], src/sift.cpp:276 -- the same float
@@ -740,8 +765,12 @@ __device__ __forceinline__ Refined refine_candidate(const Layout& Lay, const flo
 #pragma unroll
       for (int pl = 0; pl < 4; ++pl)
 #pragma unroll
-        for (int dy = 0; dy < 3; ++dy)
-          gv[pl][dy] = *reinterpret_cast<const Row3*>(gimg + O.g_off[cur - 1 + pl] + base + dy * pitch);
+        for (int dy = 0; dy < 3; ++dy) {
+          if (SPARSE && cur - 1 + pl == kScales - 1)  // plane 4: the patch at (pr, pc) == (rr_, cc_)
+            gv[pl][dy] = Row3{patch[3 * dy], patch[3 * dy + 1], patch[3 * dy + 2]};
+          else
+            gv[pl][dy] = *reinterpret_cast<const Row3*>(gimg + O.g_off[cur - 1 + pl] + base + dy * pitch);
+        }
 #pragma unroll
       for (int l = 0; l < 3; ++l)
 #pragma unroll
@@ -766,6 +795,14 @@ __device__ __forceinline__ Refined refine_candidate(const Layout& Lay, const flo
 // so the cube indices fold to constants
 #define AT(pl, yy, xx) cube[(pl) - (layer - 1)][(yy) - r + 1][(xx) - c + 1]
   for (; it < kMaxInterp; ++it) {
+    if (SPARSE && layer == kLayers && (r != pr || c != pc)) {
+      R.pending = true;
+      R.it = it;
+      R.layer = layer;
+      R.r = r;
+      R.c = c;
+      return R;
+    }
     load_cube(layer, r, c);
     const int cur = layer, lo = layer - 1, hi = layer + 1;
     const float g[3] = {(AT(cur, r, c + 1) - AT(cur, r, c - 1)) * deriv_scale,
@@ -865,6 +902,230 @@ __global__ __launch_bounds__(256) void refine_kernel(RefArgs A) {
     co->octave = R.octave;
     co->img = cd.b;
     co->npeaks = R.ok ? 1 : 0;
+    co->ref_r = R.r;
+    co->ref_c = R.c;
+    co->ref_layer = R.layer;
+  }
+}
+
+// ---- sparse flow: plane 4 point by point (SparseG4, common.hpp) -------------
+// g4_fill_kernel: Gaussian_Blur(plane 0, sig[4]) (src/sift.cpp:110-153,
+// 257-258) on the 3x3 around a candidate, for the slots that wait for it.
+// Every output runs the reference's chain -- acc = +0; kernel rows ascending,
+// columns ascending, one multiply and one add per tap; source 0 outside
+// [0, rows-1) x [0, cols-1) (:116); / 8192 -- which is blur_tile's and
+// sym_walk's chain for that pixel, so the floats are the dense plane's.
+//
+// A wave takes kG4Chunk slots, lists those that wait, and serves them
+// kG4Cands at a time: lane 3q + dy owns output row dy of candidate q, its
+// three outputs (dx = 0..2) as three chains side by side.  Kernel row a of
+// output row dy reads row a + dy of the candidate's 39 x 39 source window, so
+// the window's rows pass through a four-row LDS ring, one new row per step
+// (the 64 lanes load the group's 21 x 39 row segments, coalesced, one step
+// ahead); the 37 x 37 table sits in LDS and a step's row of it is read as
+// broadcasts.  Per step and lane: 10 + 10 ds_read_b128, 111 multiplies, 111
+// adds.
+constexpr int kG4W = 18, kG4K = 2 * kG4W + 1, kG4Win = kG4K + 2;
+constexpr int kG4Pitch = 40;               // ring / table row pitch (b128 reads)
+constexpr int kG4Cands = 21;               // candidates per wave pass (3 lanes each)
+constexpr int kG4Chunk = 256;              // candidate slots per wave
+constexpr int kG4Loads = (kG4Cands * kG4Pitch + 63) / 64;  // staged elements per lane and row
+static_assert(kG4Win <= kG4Pitch && kG4Pitch % 4 == 0 && 3 * kG4Cands <= 64, "fill layout");
+
+struct FillArgs {
+  Layout L;
+  const float* gpyr;
+  const float* coef4;
+  const Cand* cands;
+  const CandOut* couts;
+  const int* rstate;
+  const int* cand_total;  // nullptr: n_host slots
+  int n_host, cand_cap;
+  unsigned sparse;
+  float* patch;
+};
+
+// FIRST: the slots are the partial candidates (layer 2 of a sparse octave) at
+// their detected position; else the slots refine_step_kernel left pending, at
+// the position it recorded.
+template <bool FIRST>
+__global__ __launch_bounds__(64) void g4_fill_kernel(FillArgs A) {
+  __shared__ __attribute__((aligned(16))) float ring[kG4Cands * 4 * kG4Pitch];
+  __shared__ __attribute__((aligned(16))) float kt[kG4K * kG4Pitch];
+  __shared__ int list[kG4Chunk];
+  const int lane = threadIdx.x;
+  int n = A.cand_total ? *A.cand_total : A.n_host;
+  if (n > A.cand_cap) n = A.cand_cap;
+  const long long base = (long long)blockIdx.x * kG4Chunk;
+  if (base >= n) return;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int cnt = 0;
+#pragma unroll
+  for (int k = 0; k < kG4Chunk / 64; ++k) {
+    const long long ci = base + k * 64 + lane;
+    bool need = false;
+    if (ci < n) {
+      if (FIRST) {
+        const int ol = A.cands[ci].ol;
+        need = (ol >> 8) == kLayers && ((A.sparse >> (ol & 255)) & 1u);
+      } else {
+        need = A.rstate[ci] >= 0;
+      }
+    }
+    const unsigned long long m = __ballot(need);
+    if (need) list[cnt + __popcll(m & below)] = (int)ci;
+    cnt += __popcll(m);
+  }
+  if (cnt == 0) return;  // uniform
+  for (int i = lane; i < kG4K * kG4K; i += 64) {
+    const int a = i / kG4K;
+    kt[a * kG4Pitch + (i - a * kG4K)] = A.coef4[i];
+  }
+  wave_sync();
+  const int q = lane / 3, dy = lane - 3 * q;
+  for (int g0 = 0; g0 < cnt; g0 += kG4Cands) {
+    const int ng = min(kG4Cands, cnt - g0);
+    // staging: element e = k * 64 + lane of the group's row is column e % 40
+    // of candidate e / 40; its source column, row range and ring word
+    const float* sp[kG4Loads];
+    int row0[kG4Loads], spitch[kG4Loads], lim[kG4Loads], loff[kG4Loads];
+#pragma unroll
+    for (int k = 0; k < kG4Loads; ++k) {
+      const int e = k * 64 + lane, eq = e / kG4Pitch, col = e - eq * kG4Pitch;
+      sp[k] = A.gpyr;
+      row0[k] = 0;
+      spitch[k] = 0;
+      lim[k] = 0;  // no row passes
+      loff[k] = -1;
+      if (eq < ng && col < kG4Win) {
+        const int ci = list[g0 + eq];
+        const Cand cd = A.cands[ci];
+        const Octave& O = A.L.oct[cd.ol & 255];
+        const int r = FIRST ? cd.r : A.couts[ci].ref_r, c = FIRST ? cd.c : A.couts[ci].ref_c;
+        const int x = c - (kG4W + 1) + col;
+        loff[k] = eq * 4 * kG4Pitch + col;
+        row0[k] = r - (kG4W + 1);
+        if (x >= 0 && x < O.cols - 1) {  // getSubMatrix's column rule; the row rule is lim
+          sp[k] = A.gpyr + cd.b * A.L.g_img + O.g_off[0] + x;
+          spitch[k] = O.pitch;
+          lim[k] = O.rows - 1;
+        }
+      }
+    }
+    float nv[kG4Loads];
+    auto fetch = [&](int s) {  // window row s
+#pragma unroll
+      for (int k = 0; k < kG4Loads; ++k) {
+        const int row = row0[k] + s;
+        nv[k] = (unsigned)row < (unsigned)lim[k] ? sp[k][(long long)row * spitch[k]] : 0.f;
+      }
+    };
+    auto stage = [&](int s) {
+#pragma unroll
+      for (int k = 0; k < kG4Loads; ++k)
+        if (loff[k] >= 0) ring[loff[k] + (s & 3) * kG4Pitch] = nv[k];
+    };
+    fetch(0);
+    stage(0);
+    fetch(1);
+    stage(1);
+    fetch(2);
+    float acc[3] = {0.f, 0.f, 0.f};
+    // step a: window rows a .. a + 2 are needed; row a + 2 goes into the ring
+    // slot row a - 2 left (last read at step a - 2), rows a - 1 .. a + 1 of
+    // step a - 1's reads sit in the other three
+    for (int a = 0; a < kG4K; ++a) {
+      stage(a + 2);
+      wave_sync();
+      if (a + 3 < kG4Win) fetch(a + 3);
+      float x[kG4Pitch], kr[kG4Pitch];
+      const float4* w4 = reinterpret_cast<const float4*>(ring + (min(q, kG4Cands - 1) * 4 + ((a + dy) & 3)) * kG4Pitch);
+      const float4* k4 = reinterpret_cast<const float4*>(kt + a * kG4Pitch);
+#pragma unroll
+      for (int i = 0; i < kG4Pitch / 4; ++i) {
+        const float4 v = w4[i], kv = k4[i];
+        x[4 * i] = v.x;
+        x[4 * i + 1] = v.y;
+        x[4 * i + 2] = v.z;
+        x[4 * i + 3] = v.w;
+        kr[4 * i] = kv.x;
+        kr[4 * i + 1] = kv.y;
+        kr[4 * i + 2] = kv.z;
+        kr[4 * i + 3] = kv.w;
+      }
+#pragma unroll
+      for (int b = 0; b < kG4K; ++b) {
+        float t[3];
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) t[dx] = x[b + dx] * kr[b];
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) acc[dx] = acc[dx] + t[dx];
+      }
+    }
+    if (lane < 3 * ng) {
+      float* p = A.patch + (long long)list[g0 + q] * 9 + 3 * dy;
+#pragma unroll
+      for (int dx = 0; dx < 3; ++dx) p[dx] = acc[dx] / 8192.f;
+    }
+    wave_sync();  // the next pass's first stores follow this pass's last reads
+  }
+}
+
+// One round of adjustLocalExtrema in the sparse flow, one lane per candidate
+// slot.  FIRST: every slot starts; a partial candidate first takes the nine
+// DoG 3 comparisons the extrema pass left out (src/sift.cpp:493-511, same
+// threshold side and >= / <= rule: v is compared with plane 4's patch minus
+// plane 3) and is rejected like a refinement rejection when one fails, so the
+// slot and keypoint order stay the reference's.  Later rounds resume the
+// slots that wait (rstate >= 0) and leave at once on the others.
+template <bool FIRST>
+__global__ __launch_bounds__(256) void refine_step_kernel(RefArgs A) {
+  int n = *A.cand_total;
+  if (n > A.cand_cap) n = A.cand_cap;
+  for (int ci = blockIdx.x * 256 + threadIdx.x; ci < n; ci += gridDim.x * 256) {
+    int it = 0;
+    if (!FIRST) {
+      it = A.rstate[ci];
+      if (it < 0) continue;
+    }
+    const Cand cd = A.cands[ci];
+    CandOut* co = A.couts + ci;
+    const int o = cd.ol & 255;
+    const int layer = FIRST ? cd.ol >> 8 : co->ref_layer, r = FIRST ? cd.r : co->ref_r, c = FIRST ? cd.c : co->ref_c;
+    const bool sp = (A.sparse >> o) & 1u;
+    const float* gimg = A.gpyr + cd.b * A.L.g_img;
+    const float* patch = A.patch + (long long)ci * 9;
+    // the patch holds (r, c) exactly when the slot sits on layer 2: a partial
+    // candidate's first fill, or the fill after the round that left it pending
+    const bool have = sp && layer == kLayers;
+    bool ok = true;
+    if (FIRST && have) {
+      const Octave& O = A.L.oct[o];
+      const float* g3 = gimg + O.g_off[3] + (long long)(r - 1) * O.pitch + (c - 1);
+      const float* g2 = gimg + O.g_off[2] + (long long)r * O.pitch + c;
+      const float v = g3[O.pitch + 1] - *g2;  // DoG 2 at (r, c), as the extrema pass formed it
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+          const float d3 = patch[3 * dy + dx] - g3[dy * (long long)O.pitch + dx];
+          ok = ok && (v > 0 ? v >= d3 : v <= d3);
+        }
+    }
+    Refined R{};
+    if (ok) {
+      R = sp ? refine_candidate<true, true>(A.L, nullptr, gimg, o, layer, r, c, it, patch, have ? r : -1, have ? c : -1)
+             : refine_candidate<true, false>(A.L, nullptr, gimg, o, layer, r, c);
+    }
+    const bool pending = ok && R.pending;
+    A.rstate[ci] = pending ? R.it : -1;
+    co->x = R.x;
+    co->y = R.y;
+    co->size = R.size;
+    co->response = R.response;
+    co->octave = R.octave;
+    co->img = cd.b;
+    co->npeaks = ok && R.ok && !pending ? 1 : 0;
     co->ref_r = R.r;
     co->ref_c = R.c;
     co->ref_layer = R.layer;
@@ -1314,8 +1575,12 @@ bool one_image_variants(const Layout& L, int batch) {
 }
 
 void launch_refine_orient(hipStream_t st, const Layout& L, const float* gpyr, const float2* grad,
-                          const float* dog, const MathConsts* mc, DetectBufs& D, int batch) {
+                          const float* dog, const MathConsts* mc, DetectBufs& D, int batch, SparseG4 sp) {
   RefArgs A;
+  A.sparse = dog == nullptr ? sp.sparse : 0u;
+  A.coef4 = sp.coef4;
+  A.patch = D.g4patch;
+  A.rstate = D.rstate;
   A.L = L;
   A.gpyr = gpyr;
   A.grad = grad;
@@ -1327,7 +1592,27 @@ void launch_refine_orient(hipStream_t st, const Layout& L, const float* gpyr, co
   A.cand_cap = D.cand_cap;
   A.couts = D.couts;
   A.npeaks = D.npeaks;
-  hipLaunchKernelGGL(refine_kernel, dim3(resident_grid((const void*)refine_kernel, 256, 0, 2048)), dim3(256), 0, st, A);
+  if (A.sparse) {
+    // kMaxInterp rounds of fill + step: a slot's walk loads the cube once per
+    // iteration, each load can need one new patch, and every round takes a
+    // waiting slot at least one iteration further, so none waits after the
+    // last.  Rounds after the first touch a few percent of the slots.
+    FillArgs F{L, gpyr, sp.coef4, D.cands, D.couts, D.rstate, D.cand_total, 0, D.cand_cap, A.sparse, D.g4patch};
+    const dim3 fgrid((unsigned)std::max(1, (D.cand_cap + kG4Chunk - 1) / kG4Chunk));
+    const dim3 sgrid1(resident_grid((const void*)refine_step_kernel<true>, 256, 0, 2048));
+    const dim3 sgrid(resident_grid((const void*)refine_step_kernel<false>, 256, 0, 2048));
+    for (int round = 0; round < kMaxInterp; ++round) {
+      if (round == 0) {
+        hipLaunchKernelGGL(g4_fill_kernel<true>, fgrid, dim3(64), 0, st, F);
+        hipLaunchKernelGGL(refine_step_kernel<true>, sgrid1, dim3(256), 0, st, A);
+      } else {
+        hipLaunchKernelGGL(g4_fill_kernel<false>, fgrid, dim3(64), 0, st, F);
+        hipLaunchKernelGGL(refine_step_kernel<false>, sgrid, dim3(256), 0, st, A);
+      }
+    }
+  } else {
+    hipLaunchKernelGGL(refine_kernel, dim3(resident_grid((const void*)refine_kernel, 256, 0, 2048)), dim3(256), 0, st, A);
+  }
   // batches: two candidates per lane group (orient_slots_kernel<2>; three
   // slots 1.65, four 1.53-1.57 vs 1.48-1.50 ms, round 5); one image: one wave
   // per candidate with bucketed bins (orient_bin_kernel, round 4), whose chain
@@ -1356,6 +1641,13 @@ void launch_refine_orient(hipStream_t st, const Layout& L, const float* gpyr, co
     hipLaunchKernelGGL(orient_slots_kernel<2>,
                        dim3(resident_grid((const void*)orient_slots_kernel<2>, 64, 0, 8192)), dim3(64), 0, st, A);
   }
+}
+
+void launch_g4_points(hipStream_t st, const Layout& L, const float* gpyr, const float* coef4, const Cand* pts, int n,
+                      const int* n_dev, float* patch) {
+  FillArgs F{L, gpyr, coef4, pts, nullptr, nullptr, n_dev, n, n, ~0u, patch};
+  hipLaunchKernelGGL(g4_fill_kernel<true>, dim3((unsigned)std::max(1, (n + kG4Chunk - 1) / kG4Chunk)), dim3(64), 0, st,
+                     F);
 }
 
 // ---- ordered keypoint emission ------------------------------------------------

@@ -20,11 +20,27 @@ bool use_sym_blur(const sift_ctx* c, int rows, int cols, int batch) {
   return c->sym_blur && rows >= c->sym_rows && (long long)((cols + 63) / 64) * batch >= c->sym_min;
 }
 
-// Taps per output pixel of the four octave blurs: 1-D (row or column pass of
-// the separable form) or 2-D.
-double octave_taps(const sift_ctx* c, bool two_d) {
+// The sparse flow (SparseG4, common.hpp) of a SIFT_NCL batch: the octaves the
+// scatter blur takes, in exact mode; 0 for every other call.
+unsigned sparse_octaves(const sift_ctx* c, const Layout& L, int batch) {
+  if (!c->sparse_g4 || (c->flags & SIFT_FLAG_FAST)) return 0;
+  unsigned m = 0;
+  for (int o = 0; o < L.n_oct; ++o)
+    if (use_sym_blur(c, L.oct[o].rows, L.oct[o].cols, batch)) m |= 1u << o;
+  return m;
+}
+
+const float* coef4_table(const sift_ctx* c) {
+  size_t at = c->coef_oct_off;
+  for (int q = 0; q < 3; ++q) at += (size_t)(2 * c->wsz[q] + 1) * (2 * c->wsz[q] + 1);
+  return c->d_coef + at;
+}
+
+// Taps per output pixel of the octave blurs (the first n of the four scales):
+// 1-D (row or column pass of the separable form) or 2-D.
+double octave_taps(const sift_ctx* c, bool two_d, int n = 4) {
   double taps = 0;
-  for (int q = 0; q < 4; ++q) taps += two_d ? (double)(2 * c->wsz[q] + 1) * (2 * c->wsz[q] + 1) : 2 * c->wsz[q] + 1;
+  for (int q = 0; q < n; ++q) taps += two_d ? (double)(2 * c->wsz[q] + 1) * (2 * c->wsz[q] + 1) : 2 * c->wsz[q] + 1;
   return taps;
 }
 
@@ -77,7 +93,7 @@ void enqueue_poison_pad(sift_ctx* c, const Layout& L, int batch) {
 
 // Gaussian pyramid (src/sift.cpp:229-263) + DoG (:265-283) for a batch whose
 // input planes are described by src.  Async on c->stream.
-void enqueue_pyramid(sift_ctx* c, const Layout& L, Plane src, int batch, bool with_dog) {
+void enqueue_pyramid(sift_ctx* c, const Layout& L, Plane src, int batch, bool with_dog, unsigned sparse = 0) {
   hipStream_t st = c->stream;
   if (c->flags & SIFT_FLAG_FAST) {
     // separable pyramid: 24 algorithmic bytes per pixel (1 read + 5 plane
@@ -119,9 +135,12 @@ void enqueue_pyramid(sift_ctx* c, const Layout& L, Plane src, int batch, bool wi
     {
       const bool sym = use_sym_blur(c, L.oct[o].rows, L.oct[o].cols, batch);
       const bool fuse = o + 1 < L.n_oct && blur_fuses_decimation(L, o + 1);
-      StageScope s(c, sym ? ST_BLUR_SYM : ST_BLUR_OCT, 2.0 * octave_taps(c, true) * px, 20.0 * px);
+      // sparse: three planes written (1 read + 3 writes), no w = 18 taps
+      const bool no4 = sym && ((sparse >> o) & 1u);
+      StageScope s(c, sym ? ST_BLUR_SYM : ST_BLUR_OCT, 2.0 * octave_taps(c, true, no4 ? 3 : 4) * px,
+                   (no4 ? 16.0 : 20.0) * px);
       if (sym)
-        launch_blur_octave_sym(st, L, o, c->d_gpyr, batch, fuse);
+        launch_blur_octave_sym(st, L, o, c->d_gpyr, batch, fuse, no4);
       else if (blur_octave_tiles(L, o, batch) < c->small_max)
         launch_blur_octave_small(st, L, o, c->d_gpyr, c->d_coef + c->coef_oct_off, c->wsz, batch, fuse);
       else
@@ -138,15 +157,17 @@ void enqueue_pyramid(sift_ctx* c, const Layout& L, Plane src, int batch, bool wi
 // (SIFT_NCL never returns them); otherwise the DoG planes are already resident
 // (sift_find_scale_space_extrema uploads both pyramids).
 void enqueue_detect(sift_ctx* c, const Layout& L, int batch, sift_keypoint* kpts, int kp_cap,
-                    int* img_off, bool dog_from_gpyr) {
+                    int* img_off, bool dog_from_gpyr, unsigned sparse = 0) {
   hipStream_t st = c->stream;
   {
     StageScope s(c, ST_EXTREMA);
-    launch_extrema(st, L, c->d_gpyr, c->d_dog, dog_from_gpyr, c->d_grad, c->d_mc, batch, c->D);
+    launch_extrema(st, L, c->d_gpyr, c->d_dog, dog_from_gpyr, c->d_grad, c->d_mc, batch, c->D, sparse);
   }
   {
     StageScope s(c, ST_REFINE);
-    launch_refine_orient(st, L, c->d_gpyr, c->d_grad, dog_from_gpyr ? nullptr : c->d_dog.get(), c->d_mc, c->D, batch);
+    // (the sparse flow's fill and step rounds are part of this stage)
+    launch_refine_orient(st, L, c->d_gpyr, c->d_grad, dog_from_gpyr ? nullptr : c->d_dog.get(), c->d_mc, c->D, batch,
+                         SparseG4{sparse, coef4_table(c)});
   }
   {
     StageScope s(c, ST_EMIT);
@@ -208,6 +229,7 @@ int enqueue_ncl(sift_ctx* c, const float* d_imgs, int batch, int rows, int cols,
   // detection yields at most kMaxPeaks keypoints per candidate slot, so the
   // ranking scratch never needs more than that, whatever kp_cap the caller gives
   if (int rc = ensure_perm(c, (int)std::min<long long>(kp_cap, (long long)kMaxPeaks * c->D.cand_cap))) return rc;
+  const unsigned sparse = sparse_octaves(c, L, batch);
   const bool verbose = c->flags & SIFT_FLAG_VERBOSE;
   hipEvent_t v[4] = {nullptr, nullptr, nullptr, nullptr};
   auto mark = [&](int i) {
@@ -217,9 +239,9 @@ int enqueue_ncl(sift_ctx* c, const float* d_imgs, int batch, int rows, int cols,
   };
   auto body = [&]() {
     mark(0);
-    enqueue_pyramid(c, L, src, batch, false);
+    enqueue_pyramid(c, L, src, batch, false, sparse);
     mark(1);
-    enqueue_detect(c, L, batch, d_kpts, kp_cap, d_img_offsets, true);
+    enqueue_detect(c, L, batch, d_kpts, kp_cap, d_img_offsets, true, sparse);
     mark(2);
     enqueue_desc(c, L, d_kpts, d_img_offsets, batch, kp_cap, d_desc, 0, true);
     mark(3);
@@ -237,7 +259,7 @@ int enqueue_ncl(sift_ctx* c, const float* d_imgs, int batch, int rows, int cols,
   std::vector<char> key, ptrs;
   // sequence id 1, then everything that shapes the sequence; stall_once is the
   // test hook: a captured poll bound must not be replayed
-  key_put(key, 1, batch, rows, cols, row_stride, img_stride, kp_cap, c->n_oct, c->flags, c->stall_once);
+  key_put(key, 1, batch, rows, cols, row_stride, img_stride, kp_cap, c->n_oct, c->flags, c->stall_once, sparse);
   key_put(ptrs, d_imgs, d_kpts, d_desc, d_img_offsets);
   return run_graphed(c, key, ptrs, body);
 }
@@ -466,6 +488,34 @@ int sift_calc_descriptors(sift_ctx* c, const float* gpyr, int rows, int cols, in
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if ((rc = take_status(c, false, kErrAssert))) return rc;
   HIP_TRY(c, hipMemcpy(desc, c->d_desc, sizeof(float) * kDescLen * n, hipMemcpyDeviceToHost));
+  return SIFT_OK;
+}
+
+int sift_selftest_g4_points(sift_ctx* c, const float* plane, int rows, int cols, const int* rc, int n, float* out) {
+  if (int r = enter(c, plane && (n <= 0 || (rc && out)) && n >= 0, "null buffer", rows, cols, 1, 1)) return r;
+  if (n == 0) return SIFT_OK;
+  const Layout L = make_layout(rows, cols, 1);
+  std::vector<Cand> pts((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    if (abs(rc[2 * i]) >= (1 << 20) || abs(rc[2 * i + 1]) >= (1 << 20)) return fail(c, SIFT_E_INVALID, "point out of range");
+    pts[i] = Cand{0, kLayers << 8, rc[2 * i], rc[2 * i + 1]};
+  }
+  Buf<Cand> dpts;  // freed on every way out
+  Buf<float> dout;
+  HIP_TRY(c, dpts.grow((size_t)n));
+  HIP_TRY(c, dout.grow((size_t)n * 9));
+  // blocking copies and a synchronisation before every way out: the points
+  // and the two device buffers are locals the stream must not outlive
+  const size_t w = (size_t)cols * sizeof(float);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // earlier work may still use d_gpyr
+  HIP_TRY(c, hipMemcpy2D(c->d_gpyr + L.oct[0].g_off[0], L.oct[0].pitch * sizeof(float), plane, w, w, rows,
+                         hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(dpts, pts.data(), sizeof(Cand) * n, hipMemcpyHostToDevice));
+  launch_g4_points(c->stream, L, c->d_gpyr, coef4_table(c), dpts, n, nullptr, dout);
+  const hipError_t le = hipGetLastError(), se = hipStreamSynchronize(c->stream);
+  HIP_TRY(c, le);
+  HIP_TRY(c, se);
+  HIP_TRY(c, hipMemcpy(out, dout, sizeof(float) * 9 * n, hipMemcpyDeviceToHost));
   return SIFT_OK;
 }
 

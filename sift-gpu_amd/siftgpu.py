@@ -105,6 +105,7 @@ def lib():
             "sift_calc_descriptors": (ip, [vp, fp, ip, ip, ip, vp, ip, fp, ip]),
             "sift_get_stage_stats": (ip, [vp, ctypes.POINTER(StageStat), ip, pint, ip]),
             "sift_selftest_math": (ip, [vp, ip, fp, fp, fp, ip]),
+            "sift_selftest_g4_points": (ip, [vp, fp, ip, ip, pint, ip, fp]),
             "sift_knn_match_l1": (ip, [vp, fp, ip, fp, ip, ip, pint, fp]),
             "sift_bgr8_to_gray": (ip, [vp, vp, ip, ip, sz, ip, ip, fp]),
             "sift_find_homography": (ip, [fp, fp, ip, ctypes.c_double, ip, ctypes.c_double,
@@ -533,6 +534,17 @@ class Context:
         out = np.empty_like(a)
         self._check("sift_selftest_math",
                     self._L.sift_selftest_math(self.h, op, _fp(a), _fp(bb), _fp(out), a.size))
+        return out
+
+    def selftest_g4_points(self, plane: np.ndarray, rc: np.ndarray) -> np.ndarray:
+        """Gaussian_Blur(plane, sig[4]) on the 3x3 around each point (r, c) of rc [n, 2], by the
+        point evaluation of batch SIFT_NCL's sparse flow: [n, 3, 3] float32."""
+        plane = np.ascontiguousarray(plane, np.float32)
+        rc = np.ascontiguousarray(rc, np.int32).reshape(-1, 2)
+        out = np.empty((len(rc), 3, 3), np.float32)
+        self._check("sift_selftest_g4_points",
+                    self._L.sift_selftest_g4_points(self.h, _fp(plane), plane.shape[0], plane.shape[1],
+                                                    rc.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(rc), _fp(out)))
         return out
 
     def stage_stats(self, reset: bool = True):

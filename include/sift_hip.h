@@ -419,6 +419,12 @@ int sift_selftest_math(sift_ctx* ctx, int op, const float* a, const float* b, fl
  * Gaussian_Blur(plane, sig[4]) at (r + dy, c + dx), dy, dx in -1..1 -- the dense
  * blur's floats.  Points may lie anywhere with |r|, |c| < 2^20. */
 int sift_selftest_g4_points(sift_ctx* ctx, const float* plane, int rows, int cols, const int* rc, int n, float* out);
+/* Diagnostic of the same point evaluation in the last sift_detect_compute_batch
+ * call of the context (synchronises its stream; zeros when that call blurred
+ * every plane 4 densely): the slots the first fill served, the slots whose
+ * refinement then waited for a further patch, and the most fills any one slot
+ * took (at most 5, the reference's SIFT_MAX_INTERP_STEPS). */
+int sift_g4_fill_stats(sift_ctx* ctx, int* first_slots, int* waiting, int* max_fills);
 
 /* ---- profiling ------------------------------------------------------------ */
 /* With SIFT_FLAG_PROFILE: per-stage device time accumulated since the last

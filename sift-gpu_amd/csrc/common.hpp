@@ -342,14 +342,22 @@ struct DetectBufs {
   int* scan_tiles;      // per-tile sums of the multi-block scan, [scan_tiles_for(max(blk_cap, cand_cap))]
   float* g4patch;       // sparse flow: plane 4 on the 3x3 around the slot's current (r, c), [9 * cand_cap]
   int* rstate;          // sparse flow: Newton iteration a slot waits at for its patch, or -1 (done), [cand_cap]
+  int* g4wait;          // sparse flow: two lists of waiting slots, in any order, [2 * cand_cap] (g4_round_kernel)
+  int* g4stat;          // sparse flow: the call's counters below, [kG4Stats]; cleared at the head of every detection
 };
+constexpr int kG4StatFirst = 0;  // slots the first fill served
+constexpr int kG4StatWait = 1;   // [kMaxInterp]: slots waiting after the first step, after round 1, ...
+constexpr int kG4StatFills = 6;  // most fills any waiting slot took (its first fill included)
+constexpr int kG4Stats = 8;
+static_assert(kG4StatWait + kMaxInterp <= kG4StatFills, "one waiting count per round");
 // The sparse flow of SIFT_NCL's detection (exact mode, batches): bit o of
 // `sparse` marks an octave whose plane 4 was not blurred.  There the extrema
 // pass tests layer 2 against DoG 1 and DoG 2 only ("partial candidates"), and
 // plane 4 is evaluated point by point -- the reference's 37 x 37 chain,
 // g4_fill_kernel -- on the 3x3 around each candidate that sits on layer 2:
 // once for the nine DoG 3 comparisons left out, then again whenever a Newton
-// step moves a candidate on layer 2 (at most kMaxInterp rounds of fill + step).
+// step moves a candidate on layer 2 (the waiting lists and g4_round_kernel;
+// at most kMaxInterp fills per slot).
 // coef4 is the context's table of sig[4] (37 x 37, row-major).
 struct SparseG4 {
   unsigned sparse;

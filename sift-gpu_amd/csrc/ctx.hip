@@ -174,11 +174,13 @@ int alloc_candidates(sift_ctx* c, int cap) {
                   c->kp_scan.grow((size_t)cap + 1) == hipSuccess && c->npeaks.grow((size_t)cap) == hipSuccess &&
                   c->scan_tmp.grow(scan_n) == hipSuccess &&
                   c->scan_tiles.grow((size_t)scan_tiles_for((long long)scan_n) + 1) == hipSuccess &&
-                  c->g4patch.grow((size_t)cap * 9) == hipSuccess && c->rstate.grow((size_t)cap) == hipSuccess;
+                  c->g4patch.grow((size_t)cap * 9) == hipSuccess && c->rstate.grow((size_t)cap) == hipSuccess &&
+                  c->g4wait.grow((size_t)cap * 2) == hipSuccess && c->g4stat.grow(kG4Stats) == hipSuccess;
   c->D = DetectBufs{c->mask,    c->blk_counts, c->cand_total, c->img_cand_off, c->cands,    ok ? cap : 0,
                     c->couts,   c->kp_scan,    c->kp_total,   c->npeaks,       c->scan_tmp, c->scan_tiles,
-                    c->g4patch, c->rstate};
+                    c->g4patch, c->rstate,     c->g4wait,     c->g4stat};
   if (!ok) return fail(c, SIFT_E_NOMEM, "candidate workspace allocation failed");
+  HIP_TRY(c, hipMemset(c->g4stat, 0, kG4Stats * sizeof(int)));  // sift_g4_fill_stats before any detection
   return ensure_kp(c, (int)std::min<long long>((long long)cap * kKeypointsPerCandidateSlot, 1 << 28));
 }
 

@@ -113,6 +113,7 @@ struct sift_ctx {
   sift::Buf<sift::CandOut> couts;
   sift::Buf<float> g4patch;       // sparse flow (SparseG4, common.hpp): 9 floats per candidate slot
   sift::Buf<int> rstate;          //   and the slot's waiting state
+  sift::Buf<int> g4wait, g4stat;  //   the waiting list and the call's counters (sift_g4_fill_stats)
   sift::DetectBufs D{};
   int blk_cap = 0;
   sift::Buf<int> d_img_off;       // [max_batch+1] for the host entry points

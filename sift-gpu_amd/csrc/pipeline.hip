@@ -519,6 +519,21 @@ int sift_selftest_g4_points(sift_ctx* c, const float* plane, int rows, int cols,
   return SIFT_OK;
 }
 
+int sift_g4_fill_stats(sift_ctx* c, int* first_slots, int* waiting, int* max_fills) {
+  if (!c || !first_slots || !waiting || !max_fills) return SIFT_E_INVALID;
+  (void)hipSetDevice(c->device);
+  int v[kG4Stats] = {};
+  if (c->g4stat.get()) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(v, c->g4stat, sizeof(v), hipMemcpyDeviceToHost));
+  }
+  *first_slots = v[kG4StatFirst];
+  *waiting = v[kG4StatWait];
+  // a slot that never waited took its first fill only; the rounds count the others
+  *max_fills = std::max(v[kG4StatFills], v[kG4StatFirst] > 0 ? 1 : 0);
+  return SIFT_OK;
+}
+
 int sift_selftest_math(sift_ctx* c, int op, const float* a, const float* b, float* out, int n) {
   if (!c) return SIFT_E_INVALID;
   if (!a || !out || n < 0 || op < 0 || op > 9 || ((op == 1 || op == 2 || op >= 8) && !b))

@@ -106,6 +106,7 @@ def lib():
             "sift_get_stage_stats": (ip, [vp, ctypes.POINTER(StageStat), ip, pint, ip]),
             "sift_selftest_math": (ip, [vp, ip, fp, fp, fp, ip]),
             "sift_selftest_g4_points": (ip, [vp, fp, ip, ip, pint, ip, fp]),
+            "sift_g4_fill_stats": (ip, [vp, pint, pint, pint]),
             "sift_knn_match_l1": (ip, [vp, fp, ip, fp, ip, ip, pint, fp]),
             "sift_bgr8_to_gray": (ip, [vp, vp, ip, ip, sz, ip, ip, fp]),
             "sift_find_homography": (ip, [fp, fp, ip, ctypes.c_double, ip, ctypes.c_double,
@@ -141,7 +142,7 @@ def lib():
             "sift_multi_rccl_version": (ip, []),
             "sift_multi_copy_gathered": (ip, [vp, vp, fp, ip, pint]),
         }
-        optional = {"sift_graph_stats"}  # absent from older builds (A/B runs against a saved library)
+        optional = {"sift_graph_stats", "sift_g4_fill_stats"}  # absent from older builds (A/B runs against a saved library)
         for name, (res, args) in sigs.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -240,6 +241,13 @@ class Context:
         """(captures, in-place updates, instantiations) of the context's hipGraph cache."""
         v = [ctypes.c_longlong(0) for _ in range(3)]
         self._check("sift_graph_stats", self._L.sift_graph_stats(self.h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def g4_fill_stats(self):
+        """(first-fill slots, waiting slots after the first step, most fills of one slot) of the last
+        batch call's point evaluation of plane 4; zeros when it ran the dense flow."""
+        v = [ctypes.c_int(0) for _ in range(3)]
+        self._check("sift_g4_fill_stats", self._L.sift_g4_fill_stats(self.h, *[ctypes.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
     def set_candidate_capacity(self, per_image: int):

@@ -308,6 +308,50 @@ int sift_knn_match_l1_segmented(sift_ctx* ctx, const float* query, const int* q_
                                 int q_cap, const float* train, const int* t_offsets /* NULL = shared */,
                                 int t_cap, int k, int* idx, float* dist);
 
+/* ---- 8-bit descriptors and their matcher (opt-in; match_u8.hip) ------------- */
+/* The byte form of a descriptor row, 128 uint8: out[i][e] =
+ * saturate_cast<uchar>(desc[i][e] * 512.f) -- the float multiply (exact), then
+ * cvRound (ties to even), then a clamp to 0..255; the form the reference leaves
+ * commented out at src/sift.cpp:720 (SIFT_INT_DESCR_FCTR = 512).  -0.0 and
+ * negatives give 0, +inf gives 255, NaN is unspecified.
+ * Device buffers (16-byte aligned), enqueued on the context stream, no
+ * synchronisation: rows [0, min(*d_n_rows, row_cap)) are converted, all row_cap
+ * rows when d_n_rows is NULL; rows at or past that bound are not written.
+ * d_n_rows = d_img_offsets + batch (the batch call's total) needs no host value
+ * and, clamped to row_cap, follows its overflow convention. */
+int sift_descriptors_to_u8_device(sift_ctx* ctx, const float* d_desc, const int* d_n_rows /* may be NULL */,
+                                  int row_cap, uint8_t* d_out);
+/* Host buffers (synchronous), n rows: */
+int sift_descriptors_to_u8(sift_ctx* ctx, const float* desc, int n, uint8_t* out);
+
+/* sift_knn_match_l1_segmented_device on byte rows ([q_cap][128] / [t_cap][128]
+ * uint8, 16-byte aligned).  The distance is the integer sum of |a - b| over the
+ * 128 bytes taken as unsigned, at most 32,640, exact in any order; d_dist stays
+ * float and holds that integer, so sift_ratio_matches_device and everything
+ * after it take the output unchanged.  Everything else is the float form's
+ * contract word for word: segments from device offsets with every bound clamped
+ * to q_cap / t_cap, d_t_offsets == NULL for a shared train set, indices local
+ * to the train range, k of 1 or 2, ascending (distance, train index) with the
+ * lower index first at equal distance, idx -1 / dist +inf where fewer than k
+ * train rows exist, rows outside [clamp(q_offsets[0]), clamp(q_offsets[n]))
+ * untouched, n_segments == 0 or q_cap == 0: SIFT_OK with nothing enqueued, a
+ * NULL context or required buffer: SIFT_E_INVALID; enqueued on the context
+ * stream with no synchronisation (the scratch grows, with a wait, only when a
+ * call needs more than any call before it).  Consecutive frames: d_train =
+ * d_query, d_t_offsets = d_q_offsets + 1. */
+int sift_knn_match_l1_u8_segmented_device(sift_ctx* ctx, const uint8_t* d_query, const int* d_q_offsets,
+                                          int n_segments, int q_cap, const uint8_t* d_train,
+                                          const int* d_t_offsets /* NULL = shared */, int t_cap, int k, int* d_idx,
+                                          float* d_dist);
+/* Host buffers (synchronous); query has q_cap rows, train t_cap rows: */
+int sift_knn_match_l1_u8_segmented(sift_ctx* ctx, const uint8_t* query, const int* q_offsets, int n_segments,
+                                   int q_cap, const uint8_t* train, const int* t_offsets /* NULL = shared */,
+                                   int t_cap, int k, int* idx, float* dist);
+/* sift_knn_match_l1 on byte rows (host buffers, synchronous): one segment of
+ * n_query rows over all n_train rows. */
+int sift_knn_match_l1_u8(sift_ctx* ctx, const uint8_t* query, int n_query, const uint8_t* train, int n_train,
+                         int k, int* idx, float* dist);
+
 /* One kept match: cv::DMatch's queryIdx / trainIdx (local to their segments),
  * distance, and the segment in imgIdx's place.  16 bytes. */
 typedef struct sift_match {

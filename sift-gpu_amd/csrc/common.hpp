@@ -291,6 +291,19 @@ int knn_seg_splits(int q_cap, int n_segments, int t_cap, bool seg_train);
 void launch_knn_l1_seg(hipStream_t st, const float* q, const int* qoff, int n_segments, int q_cap, const float* t,
                        const int* toff, int t_cap, int k, int splits, int* tile_start, float2* part_d, int2* part_i,
                        int* idx, float* dist);
+// match_u8.hip: the byte quantiser (rows [0, min(*n_rows, row_cap)), all row_cap
+// rows with n_rows null) and the segmented L1 matcher on byte rows -- the grid
+// is knn_u8_seg_max_tiles() query tiles by knn_u8_seg_splits() train splits;
+// tile_start is [n_segments + 1] ints of scratch, the integer partials
+// [splits * q_cap] (unused when splits == 1).  launch_set_offsets writes the two
+// offsets of a one-segment call.
+void launch_desc_to_u8(hipStream_t st, const float* desc, const int* n_rows, int row_cap, uint8_t* out);
+int knn_u8_seg_max_tiles(int q_cap, int n_segments);
+int knn_u8_seg_splits(int q_cap, int n_segments, int t_cap, bool seg_train);
+void launch_knn_l1_u8_seg(hipStream_t st, const uint8_t* q, const int* qoff, int n_segments, int q_cap,
+                          const uint8_t* t, const int* toff, int t_cap, int k, int splits, int* tile_start,
+                          int2* part_d, int2* part_i, int* idx, float* dist);
+void launch_set_offsets(hipStream_t st, int* off, int a, int b);
 // Ratio test + ordered compaction + point gather; blk_scan is
 // [ratio_blocks(q_cap) + 1] ints of scratch.
 int ratio_blocks(int q_cap);

@@ -27,6 +27,7 @@
 // knn_l1_seg_kernel, then the ratio test with ordered compaction and the point
 // gather of src/main.cpp:28-52 (ratio_*_kernel); DESIGN.md §6a.
 #include "common.hpp"
+#include "match_seg.hpp"
 
 #include <float.h>
 
@@ -147,58 +148,9 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const float2* __restrict
 }
 
 // ---- segmented form: a whole batch in one launch sequence ---------------------
-// Query rows [qoff[b], qoff[b+1]) are segment b; the offsets live on the device
-// (sift_detect_compute_batch's d_img_offsets) and are never read by the host.
-// Every bound is clamped to the buffer's row capacity, because the batch call
-// leaves the true total in the last offset even when it exceeds kp_cap.
-__device__ __forceinline__ int clamp_row(int v, int cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
-
-// Largest b in [0, n) with clamp(off[b]) <= x; the caller guarantees
-// clamp(off[0]) <= x < clamp(off[n]).  Empty segments (equal offsets) are
-// skipped: the result's next offset is above x.
-__device__ __forceinline__ int seg_of(const int* __restrict__ off, int n, int cap, int x) {
-  int lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (clamp_row(off[mid], cap) <= x) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-// Prologue (one workgroup): tile_start[b] = number of 64-query tiles of the
-// segments before b, tile_start[nseg] = all tiles.  A tile never spans two
-// segments, so with segmented train it has one train range.
-__global__ __launch_bounds__(256) void seg_tiles_kernel(const int* __restrict__ qoff, int nseg, int q_cap,
-                                                        int* __restrict__ tile_start) {
-  __shared__ int wsum[4];
-  __shared__ int carry_s;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  for (int b0 = 0; b0 < nseg; b0 += 256) {
-    const int b = b0 + threadIdx.x;
-    int n = 0;
-    if (b < nseg) {
-      const int s = clamp_row(qoff[b], q_cap), e = clamp_row(qoff[b + 1], q_cap);
-      n = e > s ? (e - s + kQT - 1) / kQT : 0;
-    }
-    int v = n;  // inclusive scan over the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int u = __shfl_up(v, d);
-      if (lane >= d) v += u;
-    }
-    if (lane == 63) wsum[wv] = v;
-    __syncthreads();
-    int base = carry_s;
-    for (int w = 0; w < wv; ++w) base += wsum[w];
-    if (b < nseg) tile_start[b] = base + v - n;
-    __syncthreads();
-    if (threadIdx.x == 255) carry_s = base + v;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) tile_start[nseg] = carry_s;
-}
+// The clamped offsets (clamp_row), the segment search (seg_of) and the query-tile
+// table (seg_tiles_kernel, here with 64-query tiles) are match_seg.hpp's, shared
+// with the byte matcher.
 
 // knn_l1_kernel's tile (64 queries in VGPRs, 64-row train chunks in LDS,
 // broadcast reads) with the bounds taken from the device: grid.x covers the
@@ -445,7 +397,7 @@ int knn_seg_splits(int q_cap, int n_segments, int t_cap, bool seg_train) {
 void launch_knn_l1_seg(hipStream_t st, const float* q, const int* qoff, int n_segments, int q_cap, const float* t,
                        const int* toff, int t_cap, int k, int splits, int* tile_start, float2* part_d, int2* part_i,
                        int* idx, float* dist) {
-  hipLaunchKernelGGL(seg_tiles_kernel, dim3(1), dim3(256), 0, st, qoff, n_segments, q_cap, tile_start);
+  hipLaunchKernelGGL(seg_tiles_kernel<kQT>, dim3(1), dim3(256), 0, st, qoff, n_segments, q_cap, tile_start);
   dim3 grid(knn_seg_max_tiles(q_cap, n_segments), splits);
   hipLaunchKernelGGL(knn_l1_seg_kernel, grid, dim3(256), 0, st, q, qoff, n_segments, q_cap, t, toff, t_cap,
                      tile_start, splits, k, part_d, part_i, idx, dist);

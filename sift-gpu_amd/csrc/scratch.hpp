@@ -1,9 +1,9 @@
-// scratch.hpp -- how the matcher, front-end and segmented-homography entry
+// scratch.hpp -- how the matcher, byte-matcher, front-end and segmented-homography entry
 // points divide the context's one scratch block (sift_ctx::d_match).  Each
 // layout is described once, as a function of a Carver, and run twice: on a null
 // base to measure the block, then on the block itself.  Plain host C++ (no HIP
-// include), so that tests/cpp/scratch_layout.cpp and homography_layout.cpp
-// check every layout without a GPU.
+// include), so that tests/cpp/scratch_layout.cpp, match_u8_layout.cpp and
+// homography_layout.cpp check every layout without a GPU.
 #pragma once
 
 #include <stddef.h>
@@ -82,6 +82,40 @@ inline SegHost seg_host_layout(Carver& a, int n_segments, int q_cap, int t_cap, 
           a.take<int>((size_t)q_cap * k),          a.take<float>((size_t)q_cap * k),
           a.take<int>((size_t)n_segments + 1),     a.take_if<int>(has_t_off, (size_t)n_segments + 1),
           seg_layout(a, n_segments, q_cap, splits)};
+}
+
+// ---- 8-bit descriptors (match_u8.hip) ----
+// A byte row is kDescRow bytes.  The matcher's query tile is 64 x Q rows, but a
+// layout depends on it only through the split count the caller passes: the tile
+// table has one entry per segment whatever the tile, and the partials one per
+// (split, query row).  The partial distances are integers.
+struct KnnPartsU8 { Int2* dist; Int2* idx; };
+
+// sift_knn_match_l1_u8_segmented_device: the query-tile table, then the
+// partials of knn_u8_seg_splits() splits (none for one split).
+struct SegPartsU8 { int* tile_start; KnnPartsU8 parts; };
+inline SegPartsU8 seg_u8_layout(Carver& a, int n_segments, int q_cap, int splits) {
+  const size_t n = splits > 1 ? (size_t)splits * q_cap : 0;
+  return {a.take<int>((size_t)n_segments + 1), {a.take<Int2>(n), a.take<Int2>(n)}};
+}
+
+// sift_knn_match_l1_u8_segmented, and sift_knn_match_l1_u8 as one segment over
+// a shared train set (the library writes q_off itself): the staged byte rows,
+// results and offsets -- t_off keeps its place when the caller has no train
+// offsets, and is null then -- then the device form's pieces.
+struct SegHostU8 { uint8_t *query, *train; int* idx; float* dist; int *q_off, *t_off; SegPartsU8 seg; };
+inline SegHostU8 seg_u8_host_layout(Carver& a, int n_segments, int q_cap, int t_cap, bool has_t_off, int k,
+                                    int splits) {
+  return {a.take<uint8_t>((size_t)q_cap * kDescRow), a.take<uint8_t>(at_least_one(t_cap) * kDescRow),
+          a.take<int>((size_t)q_cap * k),            a.take<float>((size_t)q_cap * k),
+          a.take<int>((size_t)n_segments + 1),       a.take_if<int>(has_t_off, (size_t)n_segments + 1),
+          seg_u8_layout(a, n_segments, q_cap, splits)};
+}
+
+// sift_descriptors_to_u8: the staged float rows, then the byte rows.
+struct QuantHostU8 { float* desc; uint8_t* out; };
+inline QuantHostU8 quant_u8_host_layout(Carver& a, int n) {
+  return {a.take<float>((size_t)n * kDescRow), a.take<uint8_t>((size_t)n * kDescRow)};
 }
 
 // sift_ratio_matches_device: the block scan of ratio_blocks() blocks.

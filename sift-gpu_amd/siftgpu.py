@@ -116,6 +116,11 @@ def lib():
             "sift_knn_match_l1_device": (ip, [vp, vp, ip, vp, ip, ip, vp, vp]),
             "sift_knn_match_l1_segmented_device": (ip, [vp, vp, vp, ip, ip, vp, vp, ip, ip, vp, vp]),
             "sift_knn_match_l1_segmented": (ip, [vp, fp, pint, ip, ip, fp, pint, ip, ip, pint, fp]),
+            "sift_descriptors_to_u8_device": (ip, [vp, vp, vp, ip, vp]),
+            "sift_descriptors_to_u8": (ip, [vp, fp, ip, vp]),
+            "sift_knn_match_l1_u8_segmented_device": (ip, [vp, vp, vp, ip, ip, vp, vp, ip, ip, vp, vp]),
+            "sift_knn_match_l1_u8_segmented": (ip, [vp, vp, pint, ip, ip, vp, pint, ip, ip, pint, fp]),
+            "sift_knn_match_l1_u8": (ip, [vp, vp, ip, vp, ip, ip, pint, fp]),
             "sift_ratio_matches_device": (ip, [vp, vp, vp, vp, ip, ip, ctypes.c_double, vp, vp, vp, vp, vp, vp, ip,
                                                vp]),
             "sift_ratio_matches": (ip, [vp, pint, fp, pint, ip, ip, ctypes.c_double, vp, vp, ip, pint, vp, fp, fp,
@@ -469,6 +474,72 @@ class Context:
         m = int(moff[-1])
         return matches[:m], moff, (None if src is None else src[:m]), (None if dst is None else dst[:m])
 
+    # ---- 8-bit descriptors: the quantiser and the byte matcher (opt-in) --------
+    def descriptors_to_u8_device(self, desc_ptr: int, n_rows_ptr: int | None, row_cap: int, out_ptr: int):
+        """Device-pointer form (no sync): out[i][e] = saturate_cast<uchar>(desc[i][e] * 512)
+        for rows [0, min(*n_rows_ptr, row_cap)), all row_cap rows with n_rows_ptr None.
+        After detect_compute_batch: n_rows_ptr = offs_ptr + 4 * batch."""
+        self._check("sift_descriptors_to_u8_device",
+                    self._L.sift_descriptors_to_u8_device(self.h, ctypes.c_void_p(desc_ptr),
+                                                          ctypes.c_void_p(n_rows_ptr or None), row_cap,
+                                                          ctypes.c_void_p(out_ptr)))
+
+    def descriptorsToU8(self, desc: np.ndarray) -> np.ndarray:
+        """Float descriptors [n, 128] -> uint8 [n, 128] by the rule above (host arrays)."""
+        d = np.ascontiguousarray(desc, np.float32).reshape(-1, DESC_LEN)
+        out = np.empty((len(d), DESC_LEN), np.uint8)
+        self._check("sift_descriptors_to_u8",
+                    self._L.sift_descriptors_to_u8(self.h, _fp(d), len(d), out.ctypes.data))
+        return out
+
+    def knn_match_u8_segmented_device(self, query_ptr: int, q_offsets_ptr: int, n_segments: int, q_cap: int,
+                                      train_ptr: int, t_offsets_ptr: int | None, t_cap: int, k: int, idx_ptr: int,
+                                      dist_ptr: int):
+        """knn_match_segmented_device on uint8 rows (no sync): same arguments and
+        contract; dist stays float32 and holds the exact integer distance, so
+        ratio_matches_device takes the output unchanged."""
+        self._check("sift_knn_match_l1_u8_segmented_device",
+                    self._L.sift_knn_match_l1_u8_segmented_device(
+                        self.h, ctypes.c_void_p(query_ptr), ctypes.c_void_p(q_offsets_ptr), n_segments, q_cap,
+                        ctypes.c_void_p(train_ptr), ctypes.c_void_p(t_offsets_ptr or None), t_cap, k,
+                        ctypes.c_void_p(idx_ptr), ctypes.c_void_p(dist_ptr)))
+
+    @staticmethod
+    def _u8_rows(a):
+        a = np.asarray(a)
+        if a.dtype != np.uint8:
+            raise ValueError("expected uint8 descriptors")
+        return np.ascontiguousarray(a).reshape(-1, DESC_LEN)
+
+    def knnMatchU8Segmented(self, query: np.ndarray, q_offsets, train: np.ndarray, t_offsets=None, k: int = 2):
+        """knnMatchSegmented on uint8 descriptors (host arrays): idx int32, dist
+        float32 (integer-valued) [len(query), k]."""
+        q, t = self._u8_rows(query), self._u8_rows(train)
+        qo = np.ascontiguousarray(q_offsets, np.int32)
+        to = None if t_offsets is None else np.ascontiguousarray(t_offsets, np.int32)
+        if qo.ndim != 1 or len(qo) < 1 or (to is not None and to.shape != qo.shape):
+            raise ValueError("offsets must be 1-D, n_segments + 1 entries each")
+        pint = ctypes.POINTER(ctypes.c_int)
+        idx = np.full((len(q), k), -1, np.int32)
+        dist = np.full((len(q), k), np.inf, np.float32)
+        self._check("sift_knn_match_l1_u8_segmented",
+                    self._L.sift_knn_match_l1_u8_segmented(
+                        self.h, q.ctypes.data, qo.ctypes.data_as(pint), len(qo) - 1, len(q), t.ctypes.data,
+                        None if to is None else to.ctypes.data_as(pint), len(t), k, idx.ctypes.data_as(pint),
+                        _fp(dist)))
+        return idx, dist
+
+    def knnMatchU8(self, query: np.ndarray, train: np.ndarray, k: int = 2):
+        """knnMatch on uint8 descriptors: idx int32, dist float32 (integer-valued)
+        [n_query, k]; idx -1 / dist +inf where there are fewer than k train rows."""
+        q, t = self._u8_rows(query), self._u8_rows(train)
+        idx = np.empty((len(q), k), np.int32)
+        dist = np.empty((len(q), k), np.float32)
+        self._check("sift_knn_match_l1_u8",
+                    self._L.sift_knn_match_l1_u8(self.h, q.ctypes.data, len(q), t.ctypes.data, len(t), k,
+                                                 idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _fp(dist)))
+        return idx, dist
+
     # ---- a whole batch: homography per segment of the ratio stage's pairs ---
     def find_homography_segmented_device(self, src_xy_ptr: int, dst_xy_ptr: int, m_offsets_ptr: int,
                                          n_segments: int, m_cap: int, H_ptr: int, found_ptr: int,
@@ -767,8 +838,9 @@ NORM_L1 = 2  # cv::NORM_L1
 class BFMatcher:
     """`cv::BFMatcher(NORM_L1)` as the reference uses it (src/main.cpp:25-27):
     knnMatch(queryDescriptors, trainDescriptors, k) -> per query a list of up to
-    k DMatch, nearest first.  Only NORM_L1 float descriptors, k in (1, 2), no
-    masks / crossCheck (the reference uses none)."""
+    k DMatch, nearest first.  Only NORM_L1, k in (1, 2), no masks / crossCheck
+    (the reference uses none).  Float descriptors take the float matcher; two
+    uint8 arrays take the byte matcher (integer distances)."""
 
     def __init__(self, normType: int = NORM_L1, crossCheck: bool = False, ctx: Context | None = None):
         if normType != NORM_L1 or crossCheck:
@@ -777,7 +849,10 @@ class BFMatcher:
 
     def knnMatch(self, queryDescriptors, trainDescriptors, k: int = 2):
         ctx = self._ctx or _ctx(1, 1)
-        idx, dist = ctx.knnMatch(queryDescriptors, trainDescriptors, k)
+        if np.asarray(queryDescriptors).dtype == np.uint8 and np.asarray(trainDescriptors).dtype == np.uint8:
+            idx, dist = ctx.knnMatchU8(queryDescriptors, trainDescriptors, k)
+        else:
+            idx, dist = ctx.knnMatch(queryDescriptors, trainDescriptors, k)
         return [[DMatch(i, int(idx[i, j]), 0, float(dist[i, j])) for j in range(k) if idx[i, j] >= 0]
                 for i in range(len(idx))]
 

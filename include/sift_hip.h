@@ -352,6 +352,39 @@ int sift_knn_match_l1_u8_segmented(sift_ctx* ctx, const uint8_t* query, const in
 int sift_knn_match_l1_u8(sift_ctx* ctx, const uint8_t* query, int n_query, const uint8_t* train, int n_train,
                          int k, int* idx, float* dist);
 
+/* ---- squared L2 on 8-bit descriptors (opt-in; match_l2_u8.hip) --------------- */
+/* sift_knn_match_l1_u8_segmented_device with the squared Euclidean distance:
+ * d(q, t) = the integer sum of (q[e] - t[e])^2 over the 128 bytes taken as
+ * unsigned, at most 128 * 255^2 = 8,323,200 < 2^24, formed from integer matrix
+ * products and exact; d_dist stays float and holds that integer.  No square
+ * root is taken: d_dist is the SQUARED distance (cv::NORM_L2SQR), and the order
+ * of neighbours is NORM_L2's.  The ratio test on it is sift_ratio_matches[_device]
+ * unchanged with ratio * ratio passed as its ratio (d1 <= r^2 d2 on squares is
+ * sqrt(d1) <= r sqrt(d2)): 0.86 * 0.86 for the application's 0.86.  Everything
+ * else is the L1 form's contract word for word: segments from device offsets
+ * with every bound clamped to q_cap / t_cap, d_t_offsets == NULL for a shared
+ * train set, indices local to the train range, k of 1 or 2, ascending
+ * (distance, train index) with the lower index first at equal distance, idx -1
+ * / dist +inf where fewer than k train rows exist, rows outside
+ * [clamp(q_offsets[0]), clamp(q_offsets[n])) untouched, n_segments == 0 or
+ * q_cap == 0: SIFT_OK with nothing enqueued, a NULL context or required buffer:
+ * SIFT_E_INVALID; enqueued on the context stream with no synchronisation (the
+ * scratch, sized from the capacities, grows, with a wait, only when a call
+ * needs more than any call before it).  Consecutive frames: d_train = d_query,
+ * d_t_offsets = d_q_offsets + 1. */
+int sift_knn_match_l2sqr_u8_segmented_device(sift_ctx* ctx, const uint8_t* d_query, const int* d_q_offsets,
+                                             int n_segments, int q_cap, const uint8_t* d_train,
+                                             const int* d_t_offsets /* NULL = shared */, int t_cap, int k,
+                                             int* d_idx, float* d_dist);
+/* Host buffers (synchronous); query has q_cap rows, train t_cap rows: */
+int sift_knn_match_l2sqr_u8_segmented(sift_ctx* ctx, const uint8_t* query, const int* q_offsets, int n_segments,
+                                      int q_cap, const uint8_t* train, const int* t_offsets /* NULL = shared */,
+                                      int t_cap, int k, int* idx, float* dist);
+/* sift_knn_match_l1_u8 with the squared L2 distance (host buffers,
+ * synchronous): one segment of n_query rows over all n_train rows. */
+int sift_knn_match_l2sqr_u8(sift_ctx* ctx, const uint8_t* query, int n_query, const uint8_t* train, int n_train,
+                            int k, int* idx, float* dist);
+
 /* One kept match: cv::DMatch's queryIdx / trainIdx (local to their segments),
  * distance, and the segment in imgIdx's place.  16 bytes. */
 typedef struct sift_match {

@@ -1,9 +1,9 @@
 // apps.hip -- the application stages behind the C ABI (include/sift_hip.h):
-// the L1 kNN matcher, its segmented form, the byte quantiser and byte matcher,
+// the L1 kNN matcher, its segmented form, the byte quantiser and the byte matchers (L1, squared L2),
 // the ratio test with point pairs and the BGR8 front end, each in a device and a
 // host form, the one-pair homography
 // wrappers and the segmented homography and corner transform.  Host code only;
-// the kernels live in match.hip, match_u8.hip, frontend.hip and homography_batch.hip (the
+// the kernels live in match.hip, match_u8.hip, match_l2_u8.hip, frontend.hip and homography_batch.hip (the
 // one-pair homography is host code in homography.hip).  Every form carves its scratch from the context's one block
 // by a layout of scratch.hpp.
 #include "ctx.hpp"
@@ -13,7 +13,8 @@ using namespace sift;
 
 namespace {
 
-static_assert(kDescRow == kDescLen && sizeof(Float2) == sizeof(float2) && sizeof(Int2) == sizeof(int2),
+static_assert(kDescRow == kDescLen && sizeof(Float2) == sizeof(float2) && sizeof(Int2) == sizeof(int2) &&
+                  kL2PadRows == kL2NormPad,
               "scratch.hpp restates these without the HIP headers");
 float2* dev(Float2* p) { return reinterpret_cast<float2*>(p); }
 int2* dev(Int2* p) { return reinterpret_cast<int2*>(p); }
@@ -149,6 +150,18 @@ int knn_seg_u8_device(sift_ctx* c, const uint8_t* q, const int* qoff, int n_segm
     StageScope sc(c, ST_MATCH_U8);  // the work depends on offsets only the device knows
     launch_knn_l1_u8_seg(c->stream, q, qoff, n_segments, q_cap, t, toff, t_cap, k, splits, s.tile_start,
                          dev(s.parts.dist), dev(s.parts.idx), idx, dist);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
+// ---- squared L2 on the same byte rows (match_l2_u8.hip); the argument checks are check_seg_u8's ----
+int knn_seg_l2_u8_device(sift_ctx* c, const uint8_t* q, const int* qoff, int n_segments, int q_cap, const uint8_t* t,
+                         const int* toff, int t_cap, int k, int splits, int* idx, float* dist, SegPartsL2U8 s) {
+  {
+    StageScope sc(c, ST_MATCH_L2_U8);  // the work depends on offsets only the device knows
+    launch_knn_l2sqr_u8_seg(c->stream, q, qoff, n_segments, q_cap, t, toff, t_cap, k, splits, s.tile_start, s.q_norm,
+                            s.t_norm, dev(s.parts.dist), dev(s.parts.idx), idx, dist);
   }
   HIP_TRY(c, hipGetLastError());
   return SIFT_OK;
@@ -351,6 +364,80 @@ int sift_knn_match_l1_u8(sift_ctx* c, const uint8_t* query, int n_query, const u
   launch_set_offsets(c->stream, S.q_off, 0, n_query);
   if ((rc = knn_seg_u8_device(c, S.query, S.q_off, 1, n_query, S.train, nullptr, n_train, k, splits, S.idx, S.dist,
                               S.seg)))
+    return rc;
+  HIP_TRY(c, hipMemcpyAsync(idx, S.idx, (size_t)n_query * k * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(dist, S.dist, (size_t)n_query * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SIFT_OK;
+}
+
+int sift_knn_match_l2sqr_u8_segmented_device(sift_ctx* c, const uint8_t* d_query, const int* d_q_offsets,
+                                             int n_segments, int q_cap, const uint8_t* d_train,
+                                             const int* d_t_offsets, int t_cap, int k, int* d_idx, float* d_dist) {
+  int rc = check_seg_u8(c, d_query, d_q_offsets, n_segments, q_cap, d_train, t_cap, k, d_idx, d_dist);
+  if (rc || n_segments == 0 || q_cap == 0) return rc;
+  if (!aligned16(d_query, d_train)) return fail(c, SIFT_E_INVALID, kRowsUnaligned);
+  (void)hipSetDevice(c->device);
+  const int splits = knn_l2_u8_seg_splits(q_cap, n_segments, t_cap, d_t_offsets != nullptr);
+  SegPartsL2U8 S;
+  if ((rc = carve(c, &S, [&](Carver& a) { return seg_l2_u8_layout(a, n_segments, q_cap, t_cap, splits); })))
+    return rc;
+  return knn_seg_l2_u8_device(c, d_query, d_q_offsets, n_segments, q_cap, d_train, d_t_offsets, t_cap, k, splits,
+                              d_idx, d_dist, S);
+}
+
+int sift_knn_match_l2sqr_u8_segmented(sift_ctx* c, const uint8_t* query, const int* q_offsets, int n_segments,
+                                      int q_cap, const uint8_t* train, const int* t_offsets, int t_cap, int k,
+                                      int* idx, float* dist) {
+  int rc = check_seg_u8(c, query, q_offsets, n_segments, q_cap, train, t_cap, k, idx, dist);
+  if (rc || n_segments == 0 || q_cap == 0) return rc;
+  (void)hipSetDevice(c->device);
+  const int splits = knn_l2_u8_seg_splits(q_cap, n_segments, t_cap, t_offsets != nullptr);
+  SegHostL2U8 S;
+  if ((rc = carve(c, &S, [&](Carver& a) {
+         return seg_l2_u8_host_layout(a, n_segments, q_cap, t_cap, t_offsets != nullptr, k, splits);
+       })))
+    return rc;
+  const size_t row = kDescLen, ob = (size_t)(n_segments + 1) * sizeof(int);
+  HIP_TRY(c, hipMemcpyAsync(S.query, query, q_cap * row, hipMemcpyHostToDevice, c->stream));
+  if (t_cap) HIP_TRY(c, hipMemcpyAsync(S.train, train, t_cap * row, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.q_off, q_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  if (S.t_off) HIP_TRY(c, hipMemcpyAsync(S.t_off, t_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  if ((rc = knn_seg_l2_u8_device(c, S.query, S.q_off, n_segments, q_cap, S.train, S.t_off, t_cap, k, splits, S.idx,
+                                 S.dist, S.seg)))
+    return rc;
+  // only the live rows come back: the others are left untouched, as in the device form
+  const int lo = clamp_off(q_offsets[0], q_cap), hi = clamp_off(q_offsets[n_segments], q_cap);
+  if (hi > lo) {
+    const size_t n = (size_t)(hi - lo) * k, o = (size_t)lo * k;
+    HIP_TRY(c, hipMemcpyAsync(idx + o, S.idx + o, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dist + o, S.dist + o, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SIFT_OK;
+}
+
+// One segment [0, n_query) over the shared train set; the library writes the two offsets itself.
+int sift_knn_match_l2sqr_u8(sift_ctx* c, const uint8_t* query, int n_query, const uint8_t* train, int n_train, int k,
+                            int* idx, float* dist) {
+  if (!c) return SIFT_E_INVALID;
+  if (n_query < 0 || n_train < 0) return fail(c, SIFT_E_INVALID, "negative descriptor count");
+  if (k != 1 && k != 2) return fail(c, SIFT_E_INVALID, "k must be 1 or 2");
+  if (n_query == 0) return SIFT_OK;
+  if (!query || !idx || !dist || (n_train > 0 && !train)) return fail(c, SIFT_E_INVALID, "null buffer");
+  (void)hipSetDevice(c->device);
+  const int splits = knn_l2_u8_seg_splits(n_query, 1, n_train, false);
+  SegHostL2U8 S;
+  int rc;
+  if ((rc = carve(c, &S,
+                  [&](Carver& a) { return seg_l2_u8_host_layout(a, 1, n_query, n_train, false, k, splits); })))
+    return rc;
+  const size_t row = kDescLen;
+  HIP_TRY(c, hipMemcpyAsync(S.query, query, n_query * row, hipMemcpyHostToDevice, c->stream));
+  if (n_train) HIP_TRY(c, hipMemcpyAsync(S.train, train, n_train * row, hipMemcpyHostToDevice, c->stream));
+  launch_set_offsets(c->stream, S.q_off, 0, n_query);
+  if ((rc = knn_seg_l2_u8_device(c, S.query, S.q_off, 1, n_query, S.train, nullptr, n_train, k, splits, S.idx,
+                                 S.dist, S.seg)))
     return rc;
   HIP_TRY(c, hipMemcpyAsync(idx, S.idx, (size_t)n_query * k * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(dist, S.dist, (size_t)n_query * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));

@@ -57,7 +57,8 @@ class Buf {
   X(ST_UPLOAD, "upload") X(ST_DOWNLOAD, "download") X(ST_BLUR1D, "blur_1d") X(ST_PYR_FAST, "pyramid_fast") \
   X(ST_MATCH, "match") X(ST_BLUR_SYM, "blur_octave_sym") X(ST_MATCH_SEG, "match_segmented")               \
   X(ST_RATIO, "ratio_matches") X(ST_HOMOG_SEG, "homography_segmented")                                  \
-  X(ST_QUANT_U8, "descriptors_to_u8") X(ST_MATCH_U8, "match_u8_segmented")
+  X(ST_QUANT_U8, "descriptors_to_u8") X(ST_MATCH_U8, "match_u8_segmented")                               \
+  X(ST_MATCH_L2_U8, "match_l2sqr_u8_segmented")
 enum Stage {
 #define X(id, name) id,
   SIFT_STAGES(X)

@@ -2,8 +2,8 @@
 // points divide the context's one scratch block (sift_ctx::d_match).  Each
 // layout is described once, as a function of a Carver, and run twice: on a null
 // base to measure the block, then on the block itself.  Plain host C++ (no HIP
-// include), so that tests/cpp/scratch_layout.cpp, match_u8_layout.cpp and
-// homography_layout.cpp check every layout without a GPU.
+// include), so that tests/cpp/scratch_layout.cpp, match_u8_layout.cpp,
+// match_l2_u8_layout.cpp and homography_layout.cpp check every layout without a GPU.
 #pragma once
 
 #include <stddef.h>
@@ -110,6 +110,32 @@ inline SegHostU8 seg_u8_host_layout(Carver& a, int n_segments, int q_cap, int t_
           a.take<int>((size_t)q_cap * k),            a.take<float>((size_t)q_cap * k),
           a.take<int>((size_t)n_segments + 1),       a.take_if<int>(has_t_off, (size_t)n_segments + 1),
           seg_u8_layout(a, n_segments, q_cap, splits)};
+}
+
+// ---- squared L2 on 8-bit descriptors (match_l2_u8.hip) ----
+// sift_knn_match_l2sqr_u8_segmented_device: the query-tile table, one int per
+// row for the squared norms of the biased rows -- every query row, every train
+// row and kL2PadRows zero entries after them, which a tile at the end of the
+// train buffer reads and masks -- then the integer partials of
+// knn_l2_u8_seg_splits() splits (none for one split).
+constexpr int kL2PadRows = 32;  // common.hpp's kL2NormPad
+struct SegPartsL2U8 { int* tile_start; int *q_norm, *t_norm; KnnPartsU8 parts; };
+inline SegPartsL2U8 seg_l2_u8_layout(Carver& a, int n_segments, int q_cap, int t_cap, int splits) {
+  const size_t n = splits > 1 ? (size_t)splits * q_cap : 0;
+  return {a.take<int>((size_t)n_segments + 1), a.take<int>((size_t)q_cap), a.take<int>((size_t)t_cap + kL2PadRows),
+          {a.take<Int2>(n), a.take<Int2>(n)}};
+}
+
+// sift_knn_match_l2sqr_u8_segmented, and sift_knn_match_l2sqr_u8 as one segment
+// over a shared train set: seg_u8_host_layout's staging, then the device form's
+// pieces.
+struct SegHostL2U8 { uint8_t *query, *train; int* idx; float* dist; int *q_off, *t_off; SegPartsL2U8 seg; };
+inline SegHostL2U8 seg_l2_u8_host_layout(Carver& a, int n_segments, int q_cap, int t_cap, bool has_t_off, int k,
+                                         int splits) {
+  return {a.take<uint8_t>((size_t)q_cap * kDescRow), a.take<uint8_t>(at_least_one(t_cap) * kDescRow),
+          a.take<int>((size_t)q_cap * k),            a.take<float>((size_t)q_cap * k),
+          a.take<int>((size_t)n_segments + 1),       a.take_if<int>(has_t_off, (size_t)n_segments + 1),
+          seg_l2_u8_layout(a, n_segments, q_cap, t_cap, splits)};
 }
 
 // sift_descriptors_to_u8: the staged float rows, then the byte rows.

@@ -121,6 +121,9 @@ def lib():
             "sift_knn_match_l1_u8_segmented_device": (ip, [vp, vp, vp, ip, ip, vp, vp, ip, ip, vp, vp]),
             "sift_knn_match_l1_u8_segmented": (ip, [vp, vp, pint, ip, ip, vp, pint, ip, ip, pint, fp]),
             "sift_knn_match_l1_u8": (ip, [vp, vp, ip, vp, ip, ip, pint, fp]),
+            "sift_knn_match_l2sqr_u8_segmented_device": (ip, [vp, vp, vp, ip, ip, vp, vp, ip, ip, vp, vp]),
+            "sift_knn_match_l2sqr_u8_segmented": (ip, [vp, vp, pint, ip, ip, vp, pint, ip, ip, pint, fp]),
+            "sift_knn_match_l2sqr_u8": (ip, [vp, vp, ip, vp, ip, ip, pint, fp]),
             "sift_ratio_matches_device": (ip, [vp, vp, vp, vp, ip, ip, ctypes.c_double, vp, vp, vp, vp, vp, vp, ip,
                                                vp]),
             "sift_ratio_matches": (ip, [vp, pint, fp, pint, ip, ip, ctypes.c_double, vp, vp, ip, pint, vp, fp, fp,
@@ -540,6 +543,50 @@ class Context:
                                                  idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _fp(dist)))
         return idx, dist
 
+    # ---- squared L2 on 8-bit descriptors (integer MFMA; opt-in) ----------------
+    def knn_match_l2sqr_u8_segmented_device(self, query_ptr: int, q_offsets_ptr: int, n_segments: int, q_cap: int,
+                                            train_ptr: int, t_offsets_ptr: int | None, t_cap: int, k: int,
+                                            idx_ptr: int, dist_ptr: int):
+        """knn_match_u8_segmented_device with the squared L2 distance (no sync):
+        same arguments and contract; dist is float32 and holds the exact integer
+        sum of (q - t)^2, at most 8,323,200.  No square root is taken: pass
+        ratio * ratio to ratio_matches_device (0.86 ** 2 for the usual 0.86)."""
+        self._check("sift_knn_match_l2sqr_u8_segmented_device",
+                    self._L.sift_knn_match_l2sqr_u8_segmented_device(
+                        self.h, ctypes.c_void_p(query_ptr), ctypes.c_void_p(q_offsets_ptr), n_segments, q_cap,
+                        ctypes.c_void_p(train_ptr), ctypes.c_void_p(t_offsets_ptr or None), t_cap, k,
+                        ctypes.c_void_p(idx_ptr), ctypes.c_void_p(dist_ptr)))
+
+    def knnMatchL2SqrU8Segmented(self, query: np.ndarray, q_offsets, train: np.ndarray, t_offsets=None, k: int = 2):
+        """knnMatchU8Segmented with the squared L2 distance (host arrays): idx
+        int32, dist float32 (integer-valued, squared) [len(query), k]."""
+        q, t = self._u8_rows(query), self._u8_rows(train)
+        qo = np.ascontiguousarray(q_offsets, np.int32)
+        to = None if t_offsets is None else np.ascontiguousarray(t_offsets, np.int32)
+        if qo.ndim != 1 or len(qo) < 1 or (to is not None and to.shape != qo.shape):
+            raise ValueError("offsets must be 1-D, n_segments + 1 entries each")
+        pint = ctypes.POINTER(ctypes.c_int)
+        idx = np.full((len(q), k), -1, np.int32)
+        dist = np.full((len(q), k), np.inf, np.float32)
+        self._check("sift_knn_match_l2sqr_u8_segmented",
+                    self._L.sift_knn_match_l2sqr_u8_segmented(
+                        self.h, q.ctypes.data, qo.ctypes.data_as(pint), len(qo) - 1, len(q), t.ctypes.data,
+                        None if to is None else to.ctypes.data_as(pint), len(t), k, idx.ctypes.data_as(pint),
+                        _fp(dist)))
+        return idx, dist
+
+    def knnMatchL2SqrU8(self, query: np.ndarray, train: np.ndarray, k: int = 2):
+        """knnMatchU8 with the squared L2 distance: idx int32, dist float32
+        (integer-valued, squared) [n_query, k]; idx -1 / dist +inf where there
+        are fewer than k train rows."""
+        q, t = self._u8_rows(query), self._u8_rows(train)
+        idx = np.empty((len(q), k), np.int32)
+        dist = np.empty((len(q), k), np.float32)
+        self._check("sift_knn_match_l2sqr_u8",
+                    self._L.sift_knn_match_l2sqr_u8(self.h, q.ctypes.data, len(q), t.ctypes.data, len(t), k,
+                                                    idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _fp(dist)))
+        return idx, dist
+
     # ---- a whole batch: homography per segment of the ratio stage's pairs ---
     def find_homography_segmented_device(self, src_xy_ptr: int, dst_xy_ptr: int, m_offsets_ptr: int,
                                          n_segments: int, m_cap: int, H_ptr: int, found_ptr: int,
@@ -833,23 +880,33 @@ class DMatch:
 
 
 NORM_L1 = 2  # cv::NORM_L1
+NORM_L2SQR = 5  # cv::NORM_L2SQR
 
 
 class BFMatcher:
     """`cv::BFMatcher(NORM_L1)` as the reference uses it (src/main.cpp:25-27):
     knnMatch(queryDescriptors, trainDescriptors, k) -> per query a list of up to
-    k DMatch, nearest first.  Only NORM_L1, k in (1, 2), no masks / crossCheck
-    (the reference uses none).  Float descriptors take the float matcher; two
-    uint8 arrays take the byte matcher (integer distances)."""
+    k DMatch, nearest first.  k in (1, 2), no masks / crossCheck (the reference
+    uses none).  NORM_L1: float descriptors take the float matcher; two uint8
+    arrays take the byte matcher (integer distances).  NORM_L2SQR: two uint8
+    arrays only, DMatch.distance is the squared distance (for a ratio test use
+    ratio_test(matches, ratio ** 2)).  NORM_L2 (the square root) is not
+    implemented."""
 
     def __init__(self, normType: int = NORM_L1, crossCheck: bool = False, ctx: Context | None = None):
-        if normType != NORM_L1 or crossCheck:
-            raise ValueError("only BFMatcher(NORM_L1) without crossCheck is implemented")
+        if normType not in (NORM_L1, NORM_L2SQR) or crossCheck:
+            raise ValueError("only BFMatcher(NORM_L1) and BFMatcher(NORM_L2SQR) without crossCheck are implemented")
+        self._norm = normType
         self._ctx = ctx
 
     def knnMatch(self, queryDescriptors, trainDescriptors, k: int = 2):
+        both_u8 = np.asarray(queryDescriptors).dtype == np.uint8 and np.asarray(trainDescriptors).dtype == np.uint8
+        if self._norm == NORM_L2SQR and not both_u8:
+            raise ValueError("BFMatcher(NORM_L2SQR) takes two uint8 descriptor arrays")
         ctx = self._ctx or _ctx(1, 1)
-        if np.asarray(queryDescriptors).dtype == np.uint8 and np.asarray(trainDescriptors).dtype == np.uint8:
+        if self._norm == NORM_L2SQR:
+            idx, dist = ctx.knnMatchL2SqrU8(queryDescriptors, trainDescriptors, k)
+        elif both_u8:
             idx, dist = ctx.knnMatchU8(queryDescriptors, trainDescriptors, k)
         else:
             idx, dist = ctx.knnMatch(queryDescriptors, trainDescriptors, k)

@@ -1,0 +1,111 @@
+// The scratch layouts of the squared-L2 byte matcher's entry points
+// (sift-gpu_amd/csrc/scratch.hpp: seg_l2_u8_layout, seg_l2_u8_host_layout) at
+// their smallest and degenerate counts, without a GPU, in the manner of
+// match_u8_layout.cpp: each piece starts on a 256-byte boundary, pieces are
+// pairwise disjoint and lie inside the measured total, and the measuring pass
+// (null base) agrees with the pass on a real block.  The block is a heap
+// allocation of exactly the measured size and every piece is written end to
+// end, so an address sanitizer build also sees any piece that leaves it.
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <functional>
+
+#include "../../sift-gpu_amd/csrc/scratch.hpp"
+
+using namespace sift;
+
+static int failures = 0;
+#define CHECK(cond, ...)                \
+  do {                                  \
+    if (!(cond)) {                      \
+      ++failures;                       \
+      printf("FAIL %s: ", what);        \
+      printf(__VA_ARGS__);              \
+      printf(" [%s]\n", #cond);         \
+    }                                   \
+  } while (0)
+
+static void run(const char* what, int n_expected, const std::function<void(Carver&, char*)>& layout) {
+  Carver measure(nullptr);
+  layout(measure, nullptr);
+  const size_t total = measure.bytes();
+  CHECK(measure.n_pieces == n_expected, "%d pieces, expected %d", measure.n_pieces, n_expected);
+  CHECK(total % Carver::kAlign == 0, "total %zu", total);
+  char* base = static_cast<char*>(aligned_alloc(Carver::kAlign, total ? total : Carver::kAlign));
+  Carver real(base);
+  layout(real, base);
+  CHECK(real.bytes() == total && real.n_pieces == measure.n_pieces, "passes disagree: %zu vs %zu bytes", real.bytes(),
+        total);
+  for (int i = 0; i < real.n_pieces; ++i) {
+    const Carver::Piece p = real.pieces[i], m = measure.pieces[i];
+    CHECK(p.off == m.off && p.bytes == m.bytes, "piece %d differs between the passes", i);
+    CHECK(p.off % Carver::kAlign == 0, "piece %d at %zu", i, p.off);
+    CHECK(p.off + p.bytes <= total, "piece %d ends at %zu of %zu", i, p.off + p.bytes, total);
+    for (int j = 0; j < i; ++j) {
+      const Carver::Piece q = real.pieces[j];
+      CHECK(p.off >= q.off + q.bytes || q.off >= p.off + p.bytes, "pieces %d and %d overlap", j, i);
+    }
+    if (p.off + p.bytes <= total) memset(base + p.off, 0xA5, p.bytes);
+  }
+  free(base);
+}
+
+// The pointer a layout returned is piece i of the carver (or null when measuring).
+#define AT(ptr, i)                                                                                      \
+  do {                                                                                                  \
+    const int i_ = (i);                                                                                 \
+    const char* p_ = reinterpret_cast<const char*>(ptr);                                                \
+    CHECK(base ? p_ == base + a.pieces[i_].off : p_ == nullptr, "field %s is not piece %d", #ptr, i_);  \
+  } while (0)
+
+int main() {
+  char what[160];
+  for (int splits : {1, 4})
+    for (int k : {1, 2})
+      for (int t_cap : {0, 7, 33})
+        for (bool t_off : {false, true})
+          for (int n_seg : {1, 3})
+            for (int q_cap : {1, 5, 257}) {
+              snprintf(what, sizeof(what), "seg l2 u8 n_seg=%d q_cap=%d t_cap=%d t_off=%d k=%d splits=%d", n_seg,
+                       q_cap, t_cap, t_off, k, splits);
+              run(what, 5, [&](Carver& a, char* base) {
+                const SegPartsL2U8 s = seg_l2_u8_layout(a, n_seg, q_cap, t_cap, splits);
+                AT(s.tile_start, 0);
+                AT(s.q_norm, 1);
+                AT(s.t_norm, 2);
+                AT(s.parts.dist, 3);
+                AT(s.parts.idx, 4);
+                CHECK(a.pieces[0].bytes == (size_t)(n_seg + 1) * 4, "one tile count per segment and the total");
+                CHECK(a.pieces[1].bytes == (size_t)q_cap * 4, "one norm per query row");
+                CHECK(a.pieces[2].bytes == (size_t)(t_cap + 32) * 4, "one norm per train row and a tile of padding");
+                CHECK(a.pieces[3].bytes == (splits > 1 ? (size_t)splits * q_cap * 8 : 0) &&
+                          a.pieces[4].bytes == a.pieces[3].bytes,
+                      "partials only above one split");
+              });
+              run(what, 11, [&](Carver& a, char* base) {
+                const SegHostL2U8 s = seg_l2_u8_host_layout(a, n_seg, q_cap, t_cap, t_off, k, splits);
+                AT(s.query, 0);
+                AT(s.train, 1);
+                AT(s.idx, 2);
+                AT(s.dist, 3);
+                AT(s.q_off, 4);
+                if (t_off) AT(s.t_off, 5);
+                CHECK(t_off || s.t_off == nullptr, "t_off without train offsets");
+                AT(s.seg.tile_start, 6);
+                AT(s.seg.q_norm, 7);
+                AT(s.seg.t_norm, 8);
+                AT(s.seg.parts.dist, 9);
+                AT(s.seg.parts.idx, 10);
+                CHECK(a.pieces[0].bytes == (size_t)q_cap * 128, "query rows are 128 bytes");
+                CHECK(a.pieces[1].bytes == (size_t)(t_cap ? t_cap : 1) * 128, "train rows keep one element");
+                CHECK(a.pieces[2].bytes == (size_t)q_cap * k * 4 && a.pieces[3].bytes == (size_t)q_cap * k * 4,
+                      "results");
+                CHECK(a.pieces[8].bytes == (size_t)(t_cap + 32) * 4, "train norms and their padding");
+              });
+            }
+  if (failures) return printf("%d checks failed\n", failures), 1;
+  printf("match l2 u8 layouts ok\n");
+  return 0;
+}

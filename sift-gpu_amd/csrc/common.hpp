@@ -366,10 +366,11 @@ struct DetectBufs {
   int* scan_tiles;      // per-tile sums of the multi-block scan, [scan_tiles_for(max(blk_cap, cand_cap))]
   float* g4patch;       // sparse flow: plane 4 on the 3x3 around the slot's current (r, c), [9 * cand_cap]
   int* rstate;          // sparse flow: Newton iteration a slot waits at for its patch, or -1 (done), [cand_cap]
-  int* g4wait;          // sparse flow: two lists of waiting slots, in any order, [2 * cand_cap] (g4_round_kernel)
+  int* g4wait;          // sparse flow: two lists of waiting slots, in any order, [2 * cand_cap] (g4_round_kernel);
+                        //   the second, which round 1 is the first to write, holds the first fill's list until then
   int* g4stat;          // sparse flow: the call's counters below, [kG4Stats]; cleared at the head of every detection
 };
-constexpr int kG4StatFirst = 0;  // slots the first fill served
+constexpr int kG4StatFirst = 0;  // slots the first fill serves: the length of its list (g4_list_kernel)
 constexpr int kG4StatWait = 1;   // [kMaxInterp]: slots waiting after the first step, after round 1, ...
 constexpr int kG4StatFills = 6;  // most fills any waiting slot took (its first fill included)
 constexpr int kG4Stats = 8;
@@ -382,10 +383,13 @@ static_assert(kG4StatWait + kMaxInterp <= kG4StatFills, "one waiting count per r
 // once for the nine DoG 3 comparisons left out, then again whenever a Newton
 // step moves a candidate on layer 2 (the waiting lists and g4_round_kernel;
 // at most kMaxInterp fills per slot).
-// coef4 is the context's table of sig[4] (37 x 37, row-major).
+// coef4 is the context's table of sig[4] (37 x 37, row-major).  grid > 0
+// bounds the fill's and the rounds' grids (SIFT_HIP_G4_GRID, a test hook: a
+// multiple of 8; 0 = the resident grid).
 struct SparseG4 {
   unsigned sparse;
   const float* coef4;
+  int grid;
 };
 int scan_tiles_for(long long cap);
 long long mask_words_per_image(const Layout& L);
@@ -396,11 +400,12 @@ void launch_grad(hipStream_t st, const Layout& L, const float* gpyr, float2* gra
                  int s_hi, const MathConsts* mc);
 void launch_refine_orient(hipStream_t st, const Layout& L, const float* gpyr, const float2* grad,
                           const float* dog, const MathConsts* mc, DetectBufs& D, int batch,
-                          SparseG4 sp = SparseG4{0, nullptr});
+                          SparseG4 sp = SparseG4{0, nullptr, 0});
 // Test entry (sift_selftest_g4_points): plane 4's 3x3 patch around each of n
-// points of a one-octave layout whose plane 0 holds the source.
+// points of a one-octave layout whose plane 0 holds the source; grid as in
+// SparseG4.
 void launch_g4_points(hipStream_t st, const Layout& L, const float* gpyr, const float* coef4, const Cand* pts, int n,
-                      const int* n_dev, float* patch);
+                      float* patch, int grid);
 void launch_emit(hipStream_t st, DetectBufs& D, int batch, sift_keypoint* kpts, int kp_cap,
                  int* img_kp_off);
 // Device status bits; bit i <-> sticky error word err[i] (DescArgs::err_flag = &err[0],

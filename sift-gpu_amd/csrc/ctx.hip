@@ -360,6 +360,10 @@ int sift_ctx_create(int device, int max_rows, int max_cols, int max_batch, unsig
     // which sym_tables_match ties to the scatter blur's literals
     const char* dg = getenv("SIFT_HIP_DENSE_G4");
     c->sparse_g4 = c->sym_blur && !(dg && atoi(dg) != 0);
+    // test hook: small inputs reach the fill's striding and uneven XCD ranges
+    const char* gg = getenv("SIFT_HIP_G4_GRID");
+    const int g = gg ? atoi(gg) : 0;
+    c->g4_grid = g == 8 || g == 16 ? g : 0;
   }
   // SIFT_FLAG_FAST: pyramid_pc.hip carries its 1-D taps as literals; a
   // mismatch with the host formula makes the flag an error (enqueue-time check)

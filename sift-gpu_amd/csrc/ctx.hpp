@@ -105,6 +105,7 @@ struct sift_ctx {
   // SIFT_NCL on a batch, exact mode: octaves on the scatter blur skip plane 4
   // and detection evaluates it point by point (SIFT_HIP_DENSE_G4=1: off, A/B)
   bool sparse_g4 = false;
+  int g4_grid = 0;                // SIFT_HIP_G4_GRID (tests): 8 or 16 blocks for the plane-4 fill and rounds; 0 = resident
   size_t coef_base_off = 0, coef_oct_off = 0;
   sift::Buf<sift::MathConsts> d_mc;
   // detection workspace: the owners, and the raw-pointer view of them that the

@@ -941,7 +941,6 @@ constexpr int kG4Cols = 40;                // words read per window row (b128 re
 constexpr int kG4RowPitch = 44;            // ring row pitch
 constexpr int kG4CandPitch = 4 * kG4RowPitch + 4;  // ring pitch of a slot's four rows
 constexpr int kG4Cands = 21;               // slots per wave pass (3 lanes each)
-constexpr int kG4Chunk = 256;              // candidate slots a wave of the first fill scans
 constexpr int kG4Loads = (kG4Cands * kG4Cols + 63) / 64;  // staged elements per lane and row
 static_assert(kG4Win <= kG4Cols && kG4Cols <= kG4RowPitch && kG4Cols % 4 == 0 && 3 * kG4Cands <= 64, "fill layout");
 static_assert((kG4RowPitch / 4) % 2 == 1 && (kG4CandPitch / 4) % 2 == 1, "odd slot pitches (bank rule above)");
@@ -1038,51 +1037,72 @@ __device__ __forceinline__ void g4_fill_group(G4Lds& S, const Layout& L, const f
   wave_sync();  // the next pass's first stores follow this pass's last reads
 }
 
+// The groups of kG4Cands list entries one wave of a resident grid (one wave
+// per block, a multiple of 8 blocks) serves: g, g + step, ... below end.
+// XCD-aware (blocks b and b + 8 share an XCD): each XCD takes a contiguous
+// eighth of the groups and its waves hold consecutive ones at any moment, so
+// the overlapping windows of neighbouring entries meet in one L2 (speed only:
+// a patch is addressed by its slot).
+struct G4Groups {
+  int g, end, step;
+};
+__device__ __forceinline__ G4Groups g4_groups(int ngroups) {
+  const int xcd = blockIdx.x & 7, per = (ngroups + 7) / 8;
+  return G4Groups{xcd * per + (int)(blockIdx.x >> 3), min((xcd + 1) * per, ngroups), (int)(gridDim.x >> 3)};
+}
+
+// The first fill's list: every partial candidate (layer 2 of a sparse
+// octave) below min(*cand_total, cand_cap), a wave's 64 consecutive slots
+// consecutive and the waves in the order of their atomic adds (near slot
+// order, which serves locality only).  Its length is stat[kG4StatFirst].
+__global__ __launch_bounds__(256) void g4_list_kernel(const Cand* __restrict__ cands,
+                                                      const int* __restrict__ cand_total, int cand_cap,
+                                                      unsigned sparse, int* __restrict__ list,
+                                                      int* __restrict__ stat) {
+  int n = *cand_total;
+  if (n > cand_cap) n = cand_cap;
+  const int lane = threadIdx.x & 63;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const long long ci = (long long)blockIdx.x * 256 + threadIdx.x;
+  bool need = false;
+  if (ci < n) {
+    const int ol = cands[ci].ol;
+    need = (ol >> 8) == kLayers && ((sparse >> (ol & 255)) & 1u);
+  }
+  const unsigned long long m = __ballot(need);
+  if (m) {
+    const int leader = __ffsll((long long)m) - 1;
+    int at = 0;
+    if (lane == leader) at = atomicAdd(stat + kG4StatFirst, __popcll(m));
+    at = __shfl(at, leader);
+    if (need) list[at + __popcll(m & below)] = (int)ci;  // at most n <= cand_cap entries: distinct slots below n
+  }
+}
+
 struct FillArgs {
   Layout L;
   const float* gpyr;
   const float* coef4;
   const Cand* cands;
-  const int* cand_total;  // nullptr: n_host slots
+  const int* list;   // the slots to serve, *count of them (g4_list_kernel); nullptr: slots 0 .. n_host - 1
+  const int* count;
   int n_host, cand_cap;
-  unsigned sparse;
   float* patch;
-  int* stat;  // nullptr: not counted (the test entry)
 };
 
-// First fill: the partial candidates (layer 2 of a sparse octave) at their
-// detected position.  A wave takes kG4Chunk slots, lists those, and serves
-// them kG4Cands at a time.
+// First fill: the listed slots at their detected position, kG4Cands per wave
+// pass, the passes handed out by g4_groups.
 __global__ __launch_bounds__(64) void g4_fill_kernel(FillArgs A) {
   __shared__ __attribute__((aligned(16))) G4Lds S;
-  __shared__ int list[kG4Chunk];
   const int lane = threadIdx.x;
-  int n = A.cand_total ? *A.cand_total : A.n_host;
+  int n = A.list ? *A.count : A.n_host;
   if (n > A.cand_cap) n = A.cand_cap;
-  const long long base = (long long)blockIdx.x * kG4Chunk;
-  if (base >= n) return;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  int cnt = 0;
-#pragma unroll
-  for (int k = 0; k < kG4Chunk / 64; ++k) {
-    const long long ci = base + k * 64 + lane;
-    bool need = false;
-    if (ci < n) {
-      const int ol = A.cands[ci].ol;
-      need = (ol >> 8) == kLayers && ((A.sparse >> (ol & 255)) & 1u);
-    }
-    const unsigned long long m = __ballot(need);
-    if (need) list[cnt + __popcll(m & below)] = (int)ci;
-    cnt += __popcll(m);
-  }
-  if (cnt == 0) return;  // uniform
-  if (A.stat && lane == 0) atomicAdd(A.stat + kG4StatFirst, cnt);
-  wave_sync();
-  const int q = lane / 3, dy = lane - 3 * q;
-  for (int g0 = 0; g0 < cnt; g0 += kG4Cands) {
-    const int ng = min(kG4Cands, cnt - g0);
+  const int q = min(lane / 3, kG4Cands - 1), dy = lane - 3 * (lane / 3);
+  const G4Groups G = g4_groups((n + kG4Cands - 1) / kG4Cands);
+  for (int g = G.g; g < G.end; g += G.step) {
+    const int e0 = g * kG4Cands, ng = min(kG4Cands, n - e0);
     if (lane < kG4Cands) {
-      const int ci = lane < ng ? list[g0 + lane] : -1;
+      const int ci = lane < ng ? (A.list ? A.list[e0 + lane] : e0 + lane) : -1;
       S.ci[lane] = ci;
       if (ci >= 0) {
         const Cand cd = A.cands[ci];
@@ -1091,10 +1111,11 @@ __global__ __launch_bounds__(64) void g4_fill_kernel(FillArgs A) {
       }
     }
     wave_sync();
+    const int cq = S.ci[q];  // read before the next pass rewrites S
     float acc[3];
     g4_fill_group(S, A.L, A.gpyr, A.cands, A.coef4, lane, acc);
     if (lane < 3 * ng) {
-      float* p = A.patch + (long long)list[g0 + q] * 9 + 3 * dy;
+      float* p = A.patch + (long long)cq * 9 + 3 * dy;
 #pragma unroll
       for (int dx = 0; dx < 3; ++dx) p[dx] = acc[dx] / 8192.f;
     }
@@ -1183,6 +1204,9 @@ __global__ __launch_bounds__(256) void refine_step_kernel(RefArgs A) {
 // waits (launch_refine_orient).  (One launch looping over its group until no
 // member waited cost as many passes as the group's deepest slot: 1.07 ms
 // against the 1.02 ms of the uncompacted rounds it replaced.)
+#ifndef SIFT_G4_ROUND_XCD
+#define SIFT_G4_ROUND_XCD 0  // A/B builds only (tools/build_var.sh): 1 = g4_groups' order over the round lists
+#endif
 __global__ __launch_bounds__(64) void g4_round_kernel(RefArgs A, int round) {
   __shared__ __attribute__((aligned(16))) G4Lds S;
   __shared__ float pt[kG4Cands * 9];
@@ -1194,8 +1218,13 @@ __global__ __launch_bounds__(64) void g4_round_kernel(RefArgs A, int round) {
   const unsigned long long below = (1ull << lane) - 1ull;
   const int q = lane / 3, dy = lane - 3 * q;
   int most = 0;
-  for (long long g0 = (long long)blockIdx.x * kG4Cands; g0 < cnt; g0 += (long long)gridDim.x * kG4Cands) {
-    const int ng = (int)min((long long)kG4Cands, cnt - g0);
+#if SIFT_G4_ROUND_XCD
+  const G4Groups G = g4_groups((cnt + kG4Cands - 1) / kG4Cands);
+#else
+  const G4Groups G{(int)blockIdx.x, (cnt + kG4Cands - 1) / kG4Cands, (int)gridDim.x};
+#endif
+  for (int g = G.g; g < G.end; g += G.step) {
+    const int g0 = g * kG4Cands, ng = min(kG4Cands, cnt - g0);
     int ci = -1, it = 0, r = 0, c = 0;
     Cand cd{};
     if (lane < ng) {
@@ -1684,6 +1713,11 @@ bool one_image_variants(const Layout& L, int batch) {
   return batch == 1 && (long long)L.rows * L.cols <= lim;
 }
 
+// Grid of a g4_groups kernel: the resident count, or SparseG4::grid's bound.
+static unsigned g4_grid(const void* kernel, int bound) {
+  return (unsigned)(bound > 0 ? bound : resident_grid(kernel, 64, 0, 2048));
+}
+
 void launch_refine_orient(hipStream_t st, const Layout& L, const float* gpyr, const float2* grad,
                           const float* dog, const MathConsts* mc, DetectBufs& D, int batch, SparseG4 sp) {
   RefArgs A;
@@ -1711,13 +1745,23 @@ void launch_refine_orient(hipStream_t st, const Layout& L, const float* gpyr, co
     // loads the cube once per iteration, each load can need one new patch, the
     // first step leaves a slot at iteration >= 1 and every round takes it at
     // least one iteration further, so none waits after the last.
-    FillArgs F{L, gpyr, sp.coef4, D.cands, D.cand_total, 0, D.cand_cap, A.sparse, D.g4patch, D.g4stat};
-    const dim3 fgrid((unsigned)std::max(1, (D.cand_cap + kG4Chunk - 1) / kG4Chunk));
-    hipLaunchKernelGGL(g4_fill_kernel, fgrid, dim3(64), 0, st, F);
+    // The first fill's slots go onto a list first (the second waiting list's
+    // space, which nothing uses before round 1), so that a resident grid can
+    // hand them out in groups of kG4Cands.
+    int* flist = D.g4wait + D.cand_cap;
+    hipLaunchKernelGGL(g4_list_kernel, dim3((unsigned)std::max(1, (D.cand_cap + 255) / 256)), dim3(256), 0, st,
+                       D.cands, D.cand_total, D.cand_cap, A.sparse, flist, D.g4stat);
+    FillArgs F{L, gpyr, sp.coef4, D.cands, flist, D.g4stat + kG4StatFirst, 0, D.cand_cap, D.g4patch};
+    hipLaunchKernelGGL(g4_fill_kernel, dim3(g4_grid((const void*)g4_fill_kernel, sp.grid)), dim3(64), 0, st, F);
     hipLaunchKernelGGL(refine_step_kernel, dim3(resident_grid((const void*)refine_step_kernel, 256, 0, 2048)),
                        dim3(256), 0, st, A);
+#if SIFT_G4_ROUND_XCD
+    const dim3 tgrid(g4_grid((const void*)g4_round_kernel, sp.grid));
+#else
     // a wave per kG4Cands waiting slots, striding when the list is longer than the grid; the others leave at once
-    const dim3 tgrid((unsigned)std::min(8192, std::max(1, (D.cand_cap + kG4Cands - 1) / kG4Cands)));
+    const int tcap = sp.grid > 0 ? sp.grid : 8192;
+    const dim3 tgrid((unsigned)std::min(tcap, std::max(1, (D.cand_cap + kG4Cands - 1) / kG4Cands)));
+#endif
     for (int round = 1; round < kMaxInterp; ++round) hipLaunchKernelGGL(g4_round_kernel, tgrid, dim3(64), 0, st, A, round);
   } else {
     hipLaunchKernelGGL(refine_kernel, dim3(resident_grid((const void*)refine_kernel, 256, 0, 2048)), dim3(256), 0, st, A);
@@ -1753,9 +1797,9 @@ void launch_refine_orient(hipStream_t st, const Layout& L, const float* gpyr, co
 }
 
 void launch_g4_points(hipStream_t st, const Layout& L, const float* gpyr, const float* coef4, const Cand* pts, int n,
-                      const int* n_dev, float* patch) {
-  FillArgs F{L, gpyr, coef4, pts, n_dev, n, n, ~0u, patch, nullptr};
-  hipLaunchKernelGGL(g4_fill_kernel, dim3((unsigned)std::max(1, (n + kG4Chunk - 1) / kG4Chunk)), dim3(64), 0, st, F);
+                      float* patch, int grid) {
+  FillArgs F{L, gpyr, coef4, pts, nullptr, nullptr, n, n, patch};
+  hipLaunchKernelGGL(g4_fill_kernel, dim3(g4_grid((const void*)g4_fill_kernel, grid)), dim3(64), 0, st, F);
 }
 
 // ---- ordered keypoint emission ------------------------------------------------

@@ -167,7 +167,7 @@ void enqueue_detect(sift_ctx* c, const Layout& L, int batch, sift_keypoint* kpts
     StageScope s(c, ST_REFINE);
     // (the sparse flow's fill and step rounds are part of this stage)
     launch_refine_orient(st, L, c->d_gpyr, c->d_grad, dog_from_gpyr ? nullptr : c->d_dog.get(), c->d_mc, c->D, batch,
-                         SparseG4{sparse, coef4_table(c)});
+                         SparseG4{sparse, coef4_table(c), c->g4_grid});
   }
   {
     StageScope s(c, ST_EMIT);
@@ -511,7 +511,7 @@ int sift_selftest_g4_points(sift_ctx* c, const float* plane, int rows, int cols,
   HIP_TRY(c, hipMemcpy2D(c->d_gpyr + L.oct[0].g_off[0], L.oct[0].pitch * sizeof(float), plane, w, w, rows,
                          hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy(dpts, pts.data(), sizeof(Cand) * n, hipMemcpyHostToDevice));
-  launch_g4_points(c->stream, L, c->d_gpyr, coef4_table(c), dpts, n, nullptr, dout);
+  launch_g4_points(c->stream, L, c->d_gpyr, coef4_table(c), dpts, n, dout, c->g4_grid);
   const hipError_t le = hipGetLastError(), se = hipStreamSynchronize(c->stream);
   HIP_TRY(c, le);
   HIP_TRY(c, se);

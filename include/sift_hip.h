@@ -91,6 +91,32 @@ int sift_sync(sift_ctx* ctx);
  * is max(16384, max_rows * max_cols / 32), about 5x the extrema of a textured
  * 1080p image.  Reallocates the workspace (synchronises). */
 int sift_set_candidate_capacity(sift_ctx* ctx, int per_image);
+/* Per-image keypoint budget of SIFT_NCL -- OpenCV's SIFT::create(nfeatures),
+ * which the reference leaves at "all".  n_per_image = 0 (the default) keeps
+ * every keypoint and launches nothing extra.  With n > 0, for each image of a
+ * call whose keypoint count K (every orientation peak is one keypoint)
+ * exceeds n: let T be the n-th largest response among the K keypoints,
+ * counted with multiplicity; every keypoint with response >= T is kept, the
+ * others are dropped (cv::KeyPointsFilter::retainBest).  So an image keeps at
+ * least n keypoints and more than n exactly when responses tie at the cut --
+ * the peaks of one extremum share a response, so this is common -- and
+ * batch * n rows is NOT a bound on a batch's total.  An image with K <= n is
+ * unchanged.  The kept keypoints stay in the unlimited order (OpenCV's own
+ * order after retainBest is unspecified): each image's output is a
+ * subsequence of its unlimited output, and each kept keypoint's 28 bytes and
+ * 128 descriptor floats are the unlimited run's bit for bit.  The selection
+ * runs on the device before the descriptors, so dropped keypoints cost no
+ * descriptor work.  d_img_offsets, the counts, *n_out and every capacity
+ * rule (kp_cap: only the first kp_cap rows written, the true total in
+ * d_img_offsets[batch], SIFT_E_CAPACITY from sift_sync; the host calls'
+ * two-call sizing) refer to the kept keypoints: a kp_cap too small for the
+ * unlimited total but large enough for the kept total succeeds.  NaN
+ * responses (NaN images) select an unspecified, in-bounds subset.
+ * Applies to sift_detect_compute, sift_detect_compute_batch (exact and
+ * SIFT_FLAG_FAST) and sift_multi_step; not to sift_find_scale_space_extrema
+ * (OpenCV filters in detectAndCompute, not there).  n_per_image < 0 or a NULL
+ * context: SIFT_E_INVALID, the setting is unchanged. */
+int sift_set_max_features(sift_ctx* ctx, int n_per_image);
 const char* sift_version(void);
 /* hipGraph cache counters of this context: sequences captured, cached
  * executables patched in place (hipGraphExecUpdate: same shape, other
@@ -171,9 +197,10 @@ int sift_multi_destroy(sift_multi* m);
 const char* sift_multi_last_error(const sift_multi* m);
 /* The first context of device index i (sift_synth_images on that device, ...). */
 sift_ctx* sift_multi_context(sift_multi* m, int index);
-/* sift_set_octaves / sift_set_flags on every context. */
+/* sift_set_octaves / sift_set_flags / sift_set_max_features on every context. */
 int sift_multi_set_octaves(sift_multi* m, int n_octaves);
 int sift_multi_set_flags(sift_multi* m, unsigned flags);
+int sift_multi_set_max_features(sift_multi* m, int n_per_image);
 /* One step: device i detects + describes counts[i] images resident on it
  * (d_imgs[i], strides in elements as in sift_detect_compute_batch) into its
  * result slots, and the previous step's records are gathered to devices[0].

@@ -369,6 +369,7 @@ struct DetectBufs {
   int* g4wait;          // sparse flow: two lists of waiting slots, in any order, [2 * cand_cap] (g4_round_kernel);
                         //   the second, which round 1 is the first to write, holds the first fill's list until then
   int* g4stat;          // sparse flow: the call's counters below, [kG4Stats]; cleared at the head of every detection
+  int* sel_hist;        // keypoint budget, multi-workgroup form: [max_batch][kSelectPasses][kSelectBins] weight histograms
 };
 constexpr int kG4StatFirst = 0;  // slots the first fill serves: the length of its list (g4_list_kernel)
 constexpr int kG4StatWait = 1;   // [kMaxInterp]: slots waiting after the first step, after round 1, ...
@@ -408,6 +409,14 @@ void launch_g4_points(hipStream_t st, const Layout& L, const float* gpyr, const 
                       float* patch, int grid);
 void launch_emit(hipStream_t st, DetectBufs& D, int batch, sift_keypoint* kpts, int kp_cap,
                  int* img_kp_off);
+// select.hip: the per-image keypoint budget (sift_set_max_features), between
+// launch_refine_orient and launch_emit.  For every image of the batch whose
+// keypoint count exceeds n_keep, npeaks becomes 0 in each candidate slot whose
+// response is below the image's n_keep-th largest (counted once per keypoint;
+// slots that tie with it stay).  grid_form: many workgroups per image and one
+// launch per digit pass (one large image) instead of one workgroup per image.
+constexpr int kSelectBins = 256, kSelectPasses = 4;
+void launch_select_best(hipStream_t st, DetectBufs& D, int batch, int n_keep, bool grid_form);
 // Device status bits; bit i <-> sticky error word err[i] (DescArgs::err_flag = &err[0],
 // status_kernel).
 constexpr int kErrAssert = 1;      // keypoint octave/layer outside the pyramid (CV_Assert)

@@ -178,7 +178,7 @@ int alloc_candidates(sift_ctx* c, int cap) {
                   c->g4wait.grow((size_t)cap * 2) == hipSuccess && c->g4stat.grow(kG4Stats) == hipSuccess;
   c->D = DetectBufs{c->mask,    c->blk_counts, c->cand_total, c->img_cand_off, c->cands,    ok ? cap : 0,
                     c->couts,   c->kp_scan,    c->kp_total,   c->npeaks,       c->scan_tmp, c->scan_tiles,
-                    c->g4patch, c->rstate,     c->g4wait,     c->g4stat};
+                    c->g4patch, c->rstate,     c->g4wait,     c->g4stat,       c->sel_hist};
   if (!ok) return fail(c, SIFT_E_NOMEM, "candidate workspace allocation failed");
   HIP_TRY(c, hipMemset(c->g4stat, 0, kG4Stats * sizeof(int)));  // sift_g4_fill_stats before any detection
   return ensure_kp(c, (int)std::min<long long>((long long)cap * kKeypointsPerCandidateSlot, 1 << 28));
@@ -364,6 +364,9 @@ int sift_ctx_create(int device, int max_rows, int max_cols, int max_batch, unsig
     const char* gg = getenv("SIFT_HIP_G4_GRID");
     const int g = gg ? atoi(gg) : 0;
     c->g4_grid = g == 8 || g == 16 ? g : 0;
+    // the keypoint budget's select: 0 = always the multi-workgroup form
+    const char* sel = getenv("SIFT_HIP_SELECT_BLOCK_MAX");
+    if (sel) c->select_block_max = atoll(sel);
   }
   // SIFT_FLAG_FAST: pyramid_pc.hip carries its 1-D taps as literals; a
   // mismatch with the host formula makes the flag an error (enqueue-time check)
@@ -392,6 +395,7 @@ int sift_ctx_create(int device, int max_rows, int max_cols, int max_batch, unsig
   if (c->mask.grow((size_t)mask_words_per_image(L) * max_batch) != hipSuccess ||
       c->blk_counts.grow(c->blk_cap) != hipSuccess || c->cand_total.grow(1) != hipSuccess ||
       c->img_cand_off.grow(max_batch + 1) != hipSuccess || c->kp_total.grow(1) != hipSuccess ||
+      c->sel_hist.grow((size_t)max_batch * kSelectPasses * kSelectBins) != hipSuccess ||
       c->d_img_off.grow(max_batch + 1) != hipSuccess || alloc_candidates(c, (int)cap) != SIFT_OK)
     return bail(SIFT_E_NOMEM);
   if (hipMemset(c->D.cand_total, 0, sizeof(int)) != hipSuccess) return bail(SIFT_E_HIP);
@@ -444,6 +448,13 @@ int sift_set_octaves(sift_ctx* c, int n) {
   if (!c) return SIFT_E_INVALID;
   if (n < 1 || n > c->max_oct) return fail(c, SIFT_E_INVALID, "n_octaves out of range");
   c->n_oct = n;
+  return SIFT_OK;
+}
+
+int sift_set_max_features(sift_ctx* c, int n_per_image) {
+  if (!c) return SIFT_E_INVALID;
+  if (n_per_image < 0) return fail(c, SIFT_E_INVALID, "max_features must be >= 0");
+  c->max_features = n_per_image;  // part of the SIFT_NCL graph key: no captured sequence is replayed with another budget
   return SIFT_OK;
 }
 

@@ -58,7 +58,7 @@ class Buf {
   X(ST_MATCH, "match") X(ST_BLUR_SYM, "blur_octave_sym") X(ST_MATCH_SEG, "match_segmented")               \
   X(ST_RATIO, "ratio_matches") X(ST_HOMOG_SEG, "homography_segmented")                                  \
   X(ST_QUANT_U8, "descriptors_to_u8") X(ST_MATCH_U8, "match_u8_segmented")                               \
-  X(ST_MATCH_L2_U8, "match_l2sqr_u8_segmented")
+  X(ST_MATCH_L2_U8, "match_l2sqr_u8_segmented") X(ST_SELECT, "select_best")
 enum Stage {
 #define X(id, name) id,
   SIFT_STAGES(X)
@@ -117,6 +117,13 @@ struct sift_ctx {
   sift::Buf<float> g4patch;       // sparse flow (SparseG4, common.hpp): 9 floats per candidate slot
   sift::Buf<int> rstate;          //   and the slot's waiting state
   sift::Buf<int> g4wait, g4stat;  //   the waiting list and the call's counters (sift_g4_fill_stats)
+  // SIFT_NCL's per-image keypoint budget (sift_set_max_features; 0 = all) and
+  // its select (select.hip): contexts with more candidate slots per image than
+  // select_block_max run the multi-workgroup form (SIFT_HIP_SELECT_BLOCK_MAX
+  // overrides; tests), whose histograms are sel_hist
+  int max_features = 0;
+  long long select_block_max = 65536;
+  sift::Buf<int> sel_hist;
   sift::DetectBufs D{};
   int blk_cap = 0;
   sift::Buf<int> d_img_off;       // [max_batch+1] for the host entry points

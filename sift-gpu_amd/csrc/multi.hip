@@ -337,6 +337,16 @@ int sift_multi_set_octaves(sift_multi* m, int n_octaves) {
   return SIFT_OK;
 }
 
+int sift_multi_set_max_features(sift_multi* m, int n_per_image) {
+  if (!m) return SIFT_E_INVALID;
+  if (n_per_image < 0) return mfail(m, SIFT_E_INVALID, "max_features must be >= 0");  // before any context changes
+  for (sift_ctx* c : m->ctx) {
+    const int rc = sift_set_max_features(c, n_per_image);
+    if (rc) return mfail(m, rc, sift_last_error(c));
+  }
+  return SIFT_OK;
+}
+
 int sift_multi_set_flags(sift_multi* m, unsigned flags) {
   if (!m) return SIFT_E_INVALID;
   for (sift_ctx* c : m->ctx) {

@@ -156,8 +156,12 @@ void enqueue_pyramid(sift_ctx* c, const Layout& L, Plane src, int batch, bool wi
 // pyramid and refinement re-forms the few it needs, so no DoG plane is written
 // (SIFT_NCL never returns them); otherwise the DoG planes are already resident
 // (sift_find_scale_space_extrema uploads both pyramids).
+// max_features > 0 (SIFT_NCL only): each image keeps its best that many
+// keypoints by response, ties at the cut included (select.hip), before the
+// scan -- so the offsets, the emitted list and the descriptor work are the
+// kept keypoints'.
 void enqueue_detect(sift_ctx* c, const Layout& L, int batch, sift_keypoint* kpts, int kp_cap,
-                    int* img_off, bool dog_from_gpyr, unsigned sparse = 0) {
+                    int* img_off, bool dog_from_gpyr, unsigned sparse = 0, int max_features = 0) {
   hipStream_t st = c->stream;
   {
     StageScope s(c, ST_EXTREMA);
@@ -168,6 +172,10 @@ void enqueue_detect(sift_ctx* c, const Layout& L, int batch, sift_keypoint* kpts
     // (the sparse flow's fill and step rounds are part of this stage)
     launch_refine_orient(st, L, c->d_gpyr, c->d_grad, dog_from_gpyr ? nullptr : c->d_dog.get(), c->d_mc, c->D, batch,
                          SparseG4{sparse, coef4_table(c), c->g4_grid});
+  }
+  if (max_features > 0) {
+    StageScope s(c, ST_SELECT);
+    launch_select_best(st, c->D, batch, max_features, c->D.cand_cap / c->max_batch > c->select_block_max);
   }
   {
     StageScope s(c, ST_EMIT);
@@ -241,7 +249,7 @@ int enqueue_ncl(sift_ctx* c, const float* d_imgs, int batch, int rows, int cols,
     mark(0);
     enqueue_pyramid(c, L, src, batch, false, sparse);
     mark(1);
-    enqueue_detect(c, L, batch, d_kpts, kp_cap, d_img_offsets, true, sparse);
+    enqueue_detect(c, L, batch, d_kpts, kp_cap, d_img_offsets, true, sparse, c->max_features);
     mark(2);
     enqueue_desc(c, L, d_kpts, d_img_offsets, batch, kp_cap, d_desc, 0, true);
     mark(3);
@@ -259,7 +267,8 @@ int enqueue_ncl(sift_ctx* c, const float* d_imgs, int batch, int rows, int cols,
   std::vector<char> key, ptrs;
   // sequence id 1, then everything that shapes the sequence; stall_once is the
   // test hook: a captured poll bound must not be replayed
-  key_put(key, 1, batch, rows, cols, row_stride, img_stride, kp_cap, c->n_oct, c->flags, c->stall_once, sparse);
+  key_put(key, 1, batch, rows, cols, row_stride, img_stride, kp_cap, c->n_oct, c->flags, c->stall_once, sparse,
+          c->max_features);
   key_put(ptrs, d_imgs, d_kpts, d_desc, d_img_offsets);
   return run_graphed(c, key, ptrs, body);
 }

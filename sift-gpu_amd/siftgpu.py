@@ -88,6 +88,7 @@ def lib():
             "sift_set_octaves": (ip, [vp, ip]),
             "sift_sync": (ip, [vp]),
             "sift_set_candidate_capacity": (ip, [vp, ip]),
+            "sift_set_max_features": (ip, [vp, ip]),
             "sift_version": (ctypes.c_char_p, []),
             "sift_graph_stats": (ip, [vp, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong),
                                       ctypes.POINTER(ctypes.c_longlong)]),
@@ -138,6 +139,7 @@ def lib():
             "sift_multi_create": (ip, [pint, ip, ip, ip, ip, ctypes.c_uint, ip, ip, ip, ctypes.POINTER(vp)]),
             "sift_multi_set_octaves": (ip, [vp, ip]),
             "sift_multi_set_flags": (ip, [vp, ctypes.c_uint]),
+            "sift_multi_set_max_features": (ip, [vp, ip]),
             "sift_multi_destroy": (ip, [vp]),
             "sift_multi_last_error": (ctypes.c_char_p, [vp]),
             "sift_multi_context": (vp, [vp, ip]),
@@ -150,7 +152,8 @@ def lib():
             "sift_multi_rccl_version": (ip, []),
             "sift_multi_copy_gathered": (ip, [vp, vp, fp, ip, pint]),
         }
-        optional = {"sift_graph_stats", "sift_g4_fill_stats"}  # absent from older builds (A/B runs against a saved library)
+        optional = {"sift_graph_stats", "sift_g4_fill_stats", "sift_set_max_features",
+                    "sift_multi_set_max_features"}  # absent from older builds (A/B runs against a saved library)
         for name, (res, args) in sigs.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -260,6 +263,12 @@ class Context:
 
     def set_candidate_capacity(self, per_image: int):
         self._check("sift_set_candidate_capacity", self._L.sift_set_candidate_capacity(self.h, per_image))
+
+    def set_max_features(self, n: int):
+        """Per-image keypoint budget of SIFT_NCL and the batch calls (SIFT::create(nfeatures)); 0 = all.
+        Each image keeps its n best keypoints by response plus every tie at the cut, in the unlimited
+        order (cv::KeyPointsFilter::retainBest; include/sift_hip.h)."""
+        self._check("sift_set_max_features", self._L.sift_set_max_features(self.h, n))
 
     # ---- host-memory API (reference names) ------------------------------
     def SIFT_NCL(self, img: np.ndarray, row_stride_bytes: int | None = None):
@@ -751,6 +760,10 @@ class MultiContext:
 
     def set_flags(self, flags: int):
         self._check("sift_multi_set_flags", self._L.sift_multi_set_flags(self.h, flags))
+
+    def set_max_features(self, n: int):
+        """Context.set_max_features on every context."""
+        self._check("sift_multi_set_max_features", self._L.sift_multi_set_max_features(self.h, n))
 
     def synth_images(self, index: int, out_ptr: int, batch: int, rows: int, cols: int, row_stride: int,
                      img_stride: int, seed_base: int = 0):

@@ -445,6 +445,81 @@ int sift_ratio_matches(sift_ctx* ctx, const int* idx, const float* dist, const i
                        const sift_keypoint* t_kpts, int t_cap, const int* t_offsets, sift_match* matches,
                        float* src_xy, float* dst_xy, int m_cap, int* m_offsets);
 
+/* ---- cross-check: mutual nearest neighbours of a whole batch (cross_check.hip) -- */
+/* cv::BFMatcher(norm, crossCheck = true) on the device: (q, t) is kept only if
+ * t is q's nearest train row and q is t's nearest query row.  The two
+ * directions are two runs of a segmented matcher; this stage joins them.
+ * d_idx / d_dist are [q_cap][fwd_k], the forward result (query -> train) of any
+ * of the three segmented matchers; d_ridx is [t_cap][rev_k], the result of the
+ * same matcher with the sides exchanged (d_query = train, q_offsets =
+ * t_offsets, d_train = query, t_offsets = q_offsets), of which only column 0
+ * is read.  fwd_k and rev_k are 1 or 2 and act as row strides, so a k = 2
+ * result is passed unchanged.
+ * With qlo = clamp(q_offsets[b], q_cap) and tlo = clamp(t_offsets[b], t_cap),
+ * query row i of segment b is kept iff i is in [clamp(q_offsets[0]),
+ * clamp(q_offsets[n_segments])), j = idx[i][0] >= 0, tlo + j <
+ * clamp(t_offsets[b + 1], t_cap), ridx[tlo + j][0] == i - qlo and, when ratio >
+ * 0, also idx[i][1] >= 0 and (double)dist[i][0] <= ratio * (double)dist[i][1]
+ * (sift_ratio_matches_device's test; pass ratio * ratio with the squared L2
+ * matcher).  ratio == 0 is cross-check only; ratio > 0 needs fwd_k == 2; a
+ * negative or NaN ratio is SIFT_E_INVALID.  Ties follow the matchers' rule in
+ * both directions (the lower index wins at equal distance), so the kept set is
+ * a function of the two tables alone.  No value of a row outside the live range
+ * is used, and the address of the one dependent load (ridx) is bounded by the
+ * segment's train range before the load.
+ * d_t_offsets is required: one train segment per query segment.  A shared train
+ * set (NULL) is SIFT_E_INVALID -- its reverse result would be [n_segments][t_cap],
+ * which no matcher produces.
+ * The outputs are sift_ratio_matches_device's: dense records in query order
+ * within a segment and in segment order overall (an ordered scan, no atomics),
+ * segment b's records are [m_offsets[b], m_offsets[b+1]); d_m_offsets is
+ * n_segments + 1 ints and its last entry is the true total; only the first
+ * m_cap records are written; with d_q_kpts != NULL the interleaved point pairs
+ * are gathered, src = d_q_kpts[i], dst = d_t_kpts[tlo + j] (d_t_kpts has t_cap
+ * rows); with d_q_kpts == NULL d_t_kpts, d_src_xy and d_dst_xy are not used.
+ * Nothing else is written.  Enqueued on the context stream, no synchronisation
+ * and no host read of an offset (the scratch grows, with a wait, only when a
+ * call needs more than any call before it).  n_segments == 0 or q_cap == 0:
+ * SIFT_OK, nothing enqueued.  A NULL context or required buffer:
+ * SIFT_E_INVALID. */
+int sift_cross_check_matches_device(sift_ctx* ctx, const int* d_idx, const float* d_dist, int fwd_k,
+                                    const int* d_q_offsets, int n_segments, int q_cap, const int* d_ridx, int rev_k,
+                                    const int* d_t_offsets, int t_cap, double ratio,
+                                    const sift_keypoint* d_q_kpts /* may be NULL */, const sift_keypoint* d_t_kpts,
+                                    sift_match* d_matches, float* d_src_xy, float* d_dst_xy, int m_cap,
+                                    int* d_m_offsets);
+/* Host buffers (synchronous); idx / dist have q_cap rows, ridx t_cap rows,
+ * q_kpts q_cap rows and t_kpts t_cap rows: */
+int sift_cross_check_matches(sift_ctx* ctx, const int* idx, const float* dist, int fwd_k, const int* q_offsets,
+                             int n_segments, int q_cap, const int* ridx, int rev_k, const int* t_offsets, int t_cap,
+                             double ratio, const sift_keypoint* q_kpts /* may be NULL */, const sift_keypoint* t_kpts,
+                             sift_match* matches, float* src_xy, float* dst_xy, int m_cap, int* m_offsets);
+
+/* The distance of sift_cross_match_segmented_device and the type of its rows:
+ * float rows under L1 (sift_knn_match_l1_segmented_device), byte rows under L1
+ * (sift_knn_match_l1_u8_segmented_device), byte rows under squared L2
+ * (sift_knn_match_l2sqr_u8_segmented_device). */
+#define SIFT_METRIC_L1_F32 0
+#define SIFT_METRIC_L1_U8 1
+#define SIFT_METRIC_L2SQR_U8 2
+/* The whole job in one call: the forward pass of the metric's segmented matcher
+ * (k = 2 when ratio > 0, else k = 1), the reverse pass (k = 1, the sides
+ * exchanged -- derived from these arguments) and the stage above, all enqueued
+ * on the context stream with the two intermediate tables in context scratch,
+ * which is sized for all three before the first enqueue.  The result equals the
+ * three separate calls bit for bit.  d_query is [q_cap][128] and d_train
+ * [t_cap][128] rows of the metric's type, 16-byte aligned; d_t_offsets is
+ * required (see above); with SIFT_METRIC_L2SQR_U8 pass ratio * ratio.
+ * Consecutive frames of one batch need no host value: d_train = d_query,
+ * d_t_offsets = d_q_offsets + 1, t_cap = q_cap, n_segments = batch - 1.
+ * An unknown metric is SIFT_E_INVALID; everything else is the stage's
+ * contract. */
+int sift_cross_match_segmented_device(sift_ctx* ctx, int metric, const void* d_query, const int* d_q_offsets,
+                                      int n_segments, int q_cap, const void* d_train, const int* d_t_offsets,
+                                      int t_cap, double ratio, const sift_keypoint* d_q_kpts /* may be NULL */,
+                                      const sift_keypoint* d_t_kpts, sift_match* d_matches, float* d_src_xy,
+                                      float* d_dst_xy, int m_cap, int* d_m_offsets);
+
 /* ---- homography ---------------------------------------- */
 /* Replaces `findHomography(obj, scene, RANSAC)` and `perspectiveTransform`
  * (src/main.cpp:54-62): n point pairs as interleaved (x, y) floats, OpenCV's

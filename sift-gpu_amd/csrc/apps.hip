@@ -1,6 +1,7 @@
 // apps.hip -- the application stages behind the C ABI (include/sift_hip.h):
 // the L1 kNN matcher, its segmented form, the byte quantiser and the byte matchers (L1, squared L2),
-// the ratio test with point pairs and the BGR8 front end, each in a device and a
+// the ratio test with point pairs, the cross-check stage (cross_check.hip) with its one-call form
+// and the BGR8 front end, each in a device and a
 // host form, the one-pair homography
 // wrappers and the segmented homography and corner transform.  Host code only;
 // the kernels live in match.hip, match_u8.hip, match_l2_u8.hip, frontend.hip and homography_batch.hip (the
@@ -165,6 +166,91 @@ int knn_seg_l2_u8_device(sift_ctx* c, const uint8_t* q, const int* qoff, int n_s
   }
   HIP_TRY(c, hipGetLastError());
   return SIFT_OK;
+}
+
+// ---- cross-check: the join of a forward and a reverse matcher result (cross_check.hip) ----
+// The checks of the train offsets and the outputs, and of the ratio: shared with the one-call form.
+int check_cross_out(sift_ctx* c, const int* t_offsets, const sift_keypoint* q_kpts, const sift_keypoint* t_kpts,
+                    const sift_match* matches, const float* src_xy, const float* dst_xy, int m_cap,
+                    const int* m_offsets) {
+  if (!t_offsets)
+    return fail(c, SIFT_E_INVALID, "cross-check needs train offsets: a shared train set has no reverse result");
+  if (!m_offsets || (m_cap > 0 && !matches)) return fail(c, SIFT_E_INVALID, "null buffer");
+  if (q_kpts && (!t_kpts || (m_cap > 0 && (!src_xy || !dst_xy))))
+    return fail(c, SIFT_E_INVALID, "point pairs need the train keypoints and both xy buffers");
+  return SIFT_OK;
+}
+
+int check_cross_ratio(sift_ctx* c, double ratio, int fwd_k) {
+  if (!(ratio >= 0)) return fail(c, SIFT_E_INVALID, "ratio must be 0 (cross-check only) or positive");
+  if (ratio > 0 && fwd_k != 2) return fail(c, SIFT_E_INVALID, "the ratio test needs the k = 2 forward result");
+  return SIFT_OK;
+}
+
+int check_cross(sift_ctx* c, const int* idx, const float* dist, int fwd_k, const int* q_offsets, int n_segments,
+                int q_cap, const int* ridx, int rev_k, const int* t_offsets, int t_cap, double ratio,
+                const sift_keypoint* q_kpts, const sift_keypoint* t_kpts, const sift_match* matches,
+                const float* src_xy, const float* dst_xy, int m_cap, const int* m_offsets) {
+  if (!c) return SIFT_E_INVALID;
+  if (n_segments < 0 || q_cap < 0 || t_cap < 0 || m_cap < 0) return fail(c, SIFT_E_INVALID, "negative count");
+  if ((fwd_k != 1 && fwd_k != 2) || (rev_k != 1 && rev_k != 2))
+    return fail(c, SIFT_E_INVALID, "fwd_k and rev_k must be 1 or 2");
+  if (int rc = check_cross_ratio(c, ratio, fwd_k)) return rc;
+  if (n_segments == 0 || q_cap == 0) return SIFT_OK;
+  if (!idx || !dist || !q_offsets || (t_cap > 0 && !ridx)) return fail(c, SIFT_E_INVALID, "null buffer");
+  return check_cross_out(c, t_offsets, q_kpts, t_kpts, matches, src_xy, dst_xy, m_cap, m_offsets);
+}
+
+int cross_device(sift_ctx* c, const int* idx, const float* dist, int fwd_k, const int* qoff, int n_segments, int q_cap,
+                 const int* ridx, int rev_k, const int* toff, int t_cap, double ratio, const sift_keypoint* q_kpts,
+                 const sift_keypoint* t_kpts, sift_match* matches, float* src_xy, float* dst_xy, int m_cap, int* moff,
+                 int* blk_scan) {
+  {
+    StageScope sc(c, ST_CROSS, 0, (8.0 * fwd_k + 4.0) * q_cap);
+    launch_cross_check(c->stream, idx, dist, fwd_k, qoff, n_segments, q_cap, ridx, rev_k, toff, t_cap, ratio, q_kpts,
+                       t_kpts, matches, src_xy, dst_xy, m_cap, moff, blk_scan);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
+// The forward (k = fwd_k) and the reverse (k = 1, the sides exchanged) pass of
+// one metric into the tables of a CrossMatch layout.  A batch without train
+// rows has no reverse pass (and no neighbour to look up in its table).
+struct CrossArgs {
+  const void *query, *train;
+  const int *q_off, *t_off;
+  int n_segments, q_cap, t_cap, fwd_k, fwd_splits, rev_splits;
+};
+
+int cross_passes(sift_ctx* c, const CrossArgs& A, const CrossMatch<SegParts>& S) {
+  const float *q = static_cast<const float*>(A.query), *t = static_cast<const float*>(A.train);
+  if (int rc = knn_seg_device(c, q, A.q_off, A.n_segments, A.q_cap, t, A.t_off, A.t_cap, A.fwd_k, A.fwd_splits,
+                              S.tab.idx, S.tab.dist, S.fwd))
+    return rc;
+  if (A.t_cap == 0) return SIFT_OK;
+  return knn_seg_device(c, t, A.t_off, A.n_segments, A.t_cap, q, A.q_off, A.q_cap, 1, A.rev_splits, S.tab.ridx,
+                        S.tab.rdist, S.rev);
+}
+
+int cross_passes(sift_ctx* c, const CrossArgs& A, const CrossMatch<SegPartsU8>& S) {
+  const uint8_t *q = static_cast<const uint8_t*>(A.query), *t = static_cast<const uint8_t*>(A.train);
+  if (int rc = knn_seg_u8_device(c, q, A.q_off, A.n_segments, A.q_cap, t, A.t_off, A.t_cap, A.fwd_k, A.fwd_splits,
+                                 S.tab.idx, S.tab.dist, S.fwd))
+    return rc;
+  if (A.t_cap == 0) return SIFT_OK;
+  return knn_seg_u8_device(c, t, A.t_off, A.n_segments, A.t_cap, q, A.q_off, A.q_cap, 1, A.rev_splits, S.tab.ridx,
+                           S.tab.rdist, S.rev);
+}
+
+int cross_passes(sift_ctx* c, const CrossArgs& A, const CrossMatch<SegPartsL2U8>& S) {
+  const uint8_t *q = static_cast<const uint8_t*>(A.query), *t = static_cast<const uint8_t*>(A.train);
+  if (int rc = knn_seg_l2_u8_device(c, q, A.q_off, A.n_segments, A.q_cap, t, A.t_off, A.t_cap, A.fwd_k, A.fwd_splits,
+                                    S.tab.idx, S.tab.dist, S.fwd))
+    return rc;
+  if (A.t_cap == 0) return SIFT_OK;
+  return knn_seg_l2_u8_device(c, t, A.t_off, A.n_segments, A.t_cap, q, A.q_off, A.q_cap, 1, A.rev_splits, S.tab.ridx,
+                              S.tab.rdist, S.rev);
 }
 
 // ---- a whole batch: findHomography(RANSAC) per segment of the ratio stage's pairs (src/main.cpp:54-55) ----
@@ -501,6 +587,124 @@ int sift_ratio_matches(sift_ctx* c, const int* idx, const float* dist, const int
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   return SIFT_OK;
+}
+
+int sift_cross_check_matches_device(sift_ctx* c, const int* d_idx, const float* d_dist, int fwd_k,
+                                    const int* d_q_offsets, int n_segments, int q_cap, const int* d_ridx, int rev_k,
+                                    const int* d_t_offsets, int t_cap, double ratio, const sift_keypoint* d_q_kpts,
+                                    const sift_keypoint* d_t_kpts, sift_match* d_matches, float* d_src_xy,
+                                    float* d_dst_xy, int m_cap, int* d_m_offsets) {
+  int rc = check_cross(c, d_idx, d_dist, fwd_k, d_q_offsets, n_segments, q_cap, d_ridx, rev_k, d_t_offsets, t_cap,
+                       ratio, d_q_kpts, d_t_kpts, d_matches, d_src_xy, d_dst_xy, m_cap, d_m_offsets);
+  if (rc || n_segments == 0 || q_cap == 0) return rc;
+  (void)hipSetDevice(c->device);
+  int* blk_scan = nullptr;
+  if ((rc = carve(c, &blk_scan, [&](Carver& a) { return cross_layout(a, cross_blocks(q_cap)); }))) return rc;
+  return cross_device(c, d_idx, d_dist, fwd_k, d_q_offsets, n_segments, q_cap, d_ridx, rev_k, d_t_offsets, t_cap,
+                      ratio, d_q_kpts, d_t_kpts, d_matches, d_src_xy, d_dst_xy, m_cap, d_m_offsets, blk_scan);
+}
+
+int sift_cross_check_matches(sift_ctx* c, const int* idx, const float* dist, int fwd_k, const int* q_offsets,
+                             int n_segments, int q_cap, const int* ridx, int rev_k, const int* t_offsets, int t_cap,
+                             double ratio, const sift_keypoint* q_kpts, const sift_keypoint* t_kpts,
+                             sift_match* matches, float* src_xy, float* dst_xy, int m_cap, int* m_offsets) {
+  int rc = check_cross(c, idx, dist, fwd_k, q_offsets, n_segments, q_cap, ridx, rev_k, t_offsets, t_cap, ratio, q_kpts,
+                       t_kpts, matches, src_xy, dst_xy, m_cap, m_offsets);
+  if (rc || n_segments == 0 || q_cap == 0) return rc;
+  (void)hipSetDevice(c->device);
+  CrossHost S;
+  if ((rc = carve(c, &S, [&](Carver& a) {
+         return cross_host_layout(a, n_segments, q_cap, fwd_k, t_cap, rev_k, m_cap, q_kpts != nullptr,
+                                  cross_blocks(q_cap));
+       })))
+    return rc;
+  const size_t ob = (size_t)(n_segments + 1) * sizeof(int);
+  HIP_TRY(c, hipMemcpyAsync(S.idx, idx, (size_t)q_cap * fwd_k * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.dist, dist, (size_t)q_cap * fwd_k * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  if (t_cap)
+    HIP_TRY(c, hipMemcpyAsync(S.ridx, ridx, (size_t)t_cap * rev_k * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.q_off, q_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.t_off, t_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  if (q_kpts) {
+    HIP_TRY(c, hipMemcpyAsync(S.q_kpts, q_kpts, (size_t)q_cap * sizeof(sift_keypoint), hipMemcpyHostToDevice,
+                              c->stream));
+    if (t_cap)
+      HIP_TRY(c, hipMemcpyAsync(S.t_kpts, t_kpts, (size_t)t_cap * sizeof(sift_keypoint), hipMemcpyHostToDevice,
+                                c->stream));
+  }
+  if ((rc = cross_device(c, S.idx, S.dist, fwd_k, S.q_off, n_segments, q_cap, S.ridx, rev_k, S.t_off, t_cap, ratio,
+                         S.q_kpts, S.t_kpts, S.matches, S.src_xy, S.dst_xy, m_cap, S.m_off, S.blk_scan)))
+    return rc;
+  HIP_TRY(c, hipMemcpyAsync(m_offsets, S.m_off, ob, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // only the written records come back
+  const size_t n = (size_t)(m_offsets[n_segments] < m_cap ? m_offsets[n_segments] : m_cap);
+  if (n) {
+    HIP_TRY(c, hipMemcpyAsync(matches, S.matches, n * sizeof(sift_match), hipMemcpyDeviceToHost, c->stream));
+    if (q_kpts) {
+      HIP_TRY(c, hipMemcpyAsync(src_xy, S.src_xy, n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(dst_xy, S.dst_xy, n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return SIFT_OK;
+}
+
+int sift_cross_match_segmented_device(sift_ctx* c, int metric, const void* d_query, const int* d_q_offsets,
+                                      int n_segments, int q_cap, const void* d_train, const int* d_t_offsets,
+                                      int t_cap, double ratio, const sift_keypoint* d_q_kpts,
+                                      const sift_keypoint* d_t_kpts, sift_match* d_matches, float* d_src_xy,
+                                      float* d_dst_xy, int m_cap, int* d_m_offsets) {
+  if (!c) return SIFT_E_INVALID;
+  if (metric != SIFT_METRIC_L1_F32 && metric != SIFT_METRIC_L1_U8 && metric != SIFT_METRIC_L2SQR_U8)
+    return fail(c, SIFT_E_INVALID, "metric must be one of SIFT_METRIC_L1_F32, _L1_U8, _L2SQR_U8");
+  if (n_segments < 0 || q_cap < 0 || t_cap < 0 || m_cap < 0) return fail(c, SIFT_E_INVALID, "negative count");
+  const int fwd_k = ratio > 0 ? 2 : 1;
+  int rc = check_cross_ratio(c, ratio, fwd_k);
+  if (rc || n_segments == 0 || q_cap == 0) return rc;
+  if (!d_query || !d_q_offsets || (t_cap > 0 && !d_train)) return fail(c, SIFT_E_INVALID, "null buffer");
+  if ((rc = check_cross_out(c, d_t_offsets, d_q_kpts, d_t_kpts, d_matches, d_src_xy, d_dst_xy, m_cap, d_m_offsets)))
+    return rc;
+  if (!aligned16(d_query, d_train)) return fail(c, SIFT_E_INVALID, kRowsUnaligned);
+  (void)hipSetDevice(c->device);
+  // Every piece of both passes and of the stage is carved before the first
+  // enqueue: the block cannot grow (and move the tables) between the launches.
+  CrossArgs A{d_query, d_train, d_q_offsets, d_t_offsets, n_segments, q_cap, t_cap, fwd_k, 1, 1};
+  const int blocks = cross_blocks(q_cap);
+  CrossTables T;
+  if (metric == SIFT_METRIC_L1_F32) {
+    A.fwd_splits = knn_seg_splits(q_cap, n_segments, t_cap, true);
+    A.rev_splits = knn_seg_splits(t_cap, n_segments, q_cap, true);
+    CrossMatch<SegParts> S;
+    if ((rc = carve(c, &S, [&](Carver& a) {
+           return cross_match_layout(a, n_segments, q_cap, t_cap, fwd_k, A.fwd_splits, A.rev_splits, blocks);
+         })) ||
+        (rc = cross_passes(c, A, S)))
+      return rc;
+    T = S.tab;
+  } else if (metric == SIFT_METRIC_L1_U8) {
+    A.fwd_splits = knn_u8_seg_splits(q_cap, n_segments, t_cap, true);
+    A.rev_splits = knn_u8_seg_splits(t_cap, n_segments, q_cap, true);
+    CrossMatch<SegPartsU8> S;
+    if ((rc = carve(c, &S, [&](Carver& a) {
+           return cross_match_u8_layout(a, n_segments, q_cap, t_cap, fwd_k, A.fwd_splits, A.rev_splits, blocks);
+         })) ||
+        (rc = cross_passes(c, A, S)))
+      return rc;
+    T = S.tab;
+  } else {
+    A.fwd_splits = knn_l2_u8_seg_splits(q_cap, n_segments, t_cap, true);
+    A.rev_splits = knn_l2_u8_seg_splits(t_cap, n_segments, q_cap, true);
+    CrossMatch<SegPartsL2U8> S;
+    if ((rc = carve(c, &S, [&](Carver& a) {
+           return cross_match_l2_u8_layout(a, n_segments, q_cap, t_cap, fwd_k, A.fwd_splits, A.rev_splits, blocks);
+         })) ||
+        (rc = cross_passes(c, A, S)))
+      return rc;
+    T = S.tab;
+  }
+  return cross_device(c, T.idx, T.dist, fwd_k, d_q_offsets, n_segments, q_cap, T.ridx, 1, d_t_offsets, t_cap, ratio,
+                      d_q_kpts, d_t_kpts, d_matches, d_src_xy, d_dst_xy, m_cap, d_m_offsets, T.blk_scan);
 }
 
 int sift_bgr8_to_gray_device(sift_ctx* c, const uint8_t* d_bgr, int batch, int rows, int cols, size_t row_stride,

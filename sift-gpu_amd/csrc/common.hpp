@@ -322,6 +322,15 @@ void launch_ratio_matches(hipStream_t st, const int* idx, const float* dist, con
                           int q_cap, double ratio, const sift_keypoint* q_kpts, const sift_keypoint* t_kpts,
                           const int* toff, sift_match* matches, float* src_xy, float* dst_xy, int m_cap, int* moff,
                           int* blk_scan);
+// cross_check.hip: the join of a forward ([q_cap][fwd_k]) and a reverse
+// ([t_cap][rev_k], column 0 read) matcher result into the ratio stage's
+// outputs; ratio 0 = cross-check only; blk_scan is [cross_blocks(q_cap) + 1]
+// ints of scratch.
+int cross_blocks(int q_cap);
+void launch_cross_check(hipStream_t st, const int* idx, const float* dist, int fwd_k, const int* qoff, int n_segments,
+                        int q_cap, const int* ridx, int rev_k, const int* toff, int t_cap, double ratio,
+                        const sift_keypoint* q_kpts, const sift_keypoint* t_kpts, sift_match* matches, float* src_xy,
+                        float* dst_xy, int m_cap, int* moff, int* blk_scan);
 // pyramid_pc.hip (SIFT_FLAG_FAST): octave o's five planes by the separable
 // form, plus octave o+1's plane 0 when pyramid_fuses_decimation(L, o + 1)
 // (else decimate first), from a producer wave and three consumer waves

@@ -27,6 +27,7 @@
 // knn_l1_seg_kernel, then the ratio test with ordered compaction and the point
 // gather of src/main.cpp:28-52 (ratio_*_kernel); DESIGN.md §6a.
 #include "common.hpp"
+#include "block_scan.hpp"
 #include "match_seg.hpp"
 
 #include <float.h>
@@ -279,33 +280,8 @@ __global__ __launch_bounds__(kRB) void ratio_count_kernel(RatioIn R, int* __rest
   if (threadIdx.x == 0) blk_cnt[blockIdx.x] = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
 }
 
-// in-place exclusive scan of v[0..n), v[n] = total (one workgroup)
-__global__ __launch_bounds__(1024) void ratio_scan_kernel(int* __restrict__ v, int n) {
-  __shared__ int wsum[16];
-  __shared__ int carry_s;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  for (int i0 = 0; i0 < n; i0 += 1024) {
-    const int i = i0 + threadIdx.x;
-    const int x = i < n ? v[i] : 0;
-    int s = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int u = __shfl_up(s, d);
-      if (lane >= d) s += u;
-    }
-    if (lane == 63) wsum[wv] = s;
-    __syncthreads();
-    int base = carry_s;
-    for (int w = 0; w < wv; ++w) base += wsum[w];
-    if (i < n) v[i] = base + s - x;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry_s = base + s;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) v[n] = carry_s;
-}
+// the scan of the block counts (ratio_scan_kernel) is block_scan.hpp's, shared
+// with the cross-check stage
 
 struct RatioOut {
   const sift_keypoint* q_kpts;  // nullptr: no point pairs

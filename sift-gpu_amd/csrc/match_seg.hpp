@@ -1,7 +1,8 @@
 // match_seg.hpp -- what the segmented matchers share (match.hip: float
 // descriptors, 64-query tiles; match_u8.hip: byte descriptors, 64 x Q-query
 // tiles): the clamped device offsets, the segment search and the query-tile
-// table.  Device code, included by those two files only.
+// table.  Device code, included by the matchers and by cross_check.hip (the
+// offsets and the search) only.
 #pragma once
 
 #include "common.hpp"

@@ -1,9 +1,9 @@
-// scratch.hpp -- how the matcher, byte-matcher, front-end and segmented-homography entry
+// scratch.hpp -- how the matcher, byte-matcher, cross-check, front-end and segmented-homography entry
 // points divide the context's one scratch block (sift_ctx::d_match).  Each
 // layout is described once, as a function of a Carver, and run twice: on a null
 // base to measure the block, then on the block itself.  Plain host C++ (no HIP
 // include), so that tests/cpp/scratch_layout.cpp, match_u8_layout.cpp,
-// match_l2_u8_layout.cpp and homography_layout.cpp check every layout without a GPU.
+// match_l2_u8_layout.cpp, cross_check_layout.cpp and homography_layout.cpp check every layout without a GPU.
 #pragma once
 
 #include <stddef.h>
@@ -161,6 +161,58 @@ inline RatioHost ratio_host_layout(Carver& a, int n_segments, int q_cap, int t_c
           pairs ? a.take<sift_keypoint>((size_t)q_cap) : nullptr,
           pairs ? a.take<sift_keypoint>(at_least_one(t_cap)) : nullptr, a.take<sift_match>(m),
           pairs ? a.take<float>(m * 2) : nullptr, pairs ? a.take<float>(m * 2) : nullptr, ratio_layout(a, blocks)};
+}
+
+// ---- cross-check (cross_check.hip) ----
+// sift_cross_check_matches_device: the block scan of cross_blocks() blocks.
+inline int* cross_layout(Carver& a, int blocks) { return a.take<int>((size_t)blocks + 1); }
+
+// sift_cross_check_matches: the staged forward ([q_cap][fwd_k]) and reverse
+// ([t_cap][rev_k]) results and the three offset arrays, the keypoints and point
+// pairs only when the caller asks for pairs, the records, the block scan.
+struct CrossHost {
+  int* idx; float* dist; int* ridx; int *q_off, *t_off, *m_off; sift_keypoint *q_kpts, *t_kpts; sift_match* matches;
+  float *src_xy, *dst_xy; int* blk_scan;
+};
+inline CrossHost cross_host_layout(Carver& a, int n_segments, int q_cap, int fwd_k, int t_cap, int rev_k, int m_cap,
+                                   bool pairs, int blocks) {
+  const size_t offs = (size_t)n_segments + 1, m = at_least_one(m_cap);
+  return {a.take<int>((size_t)q_cap * fwd_k), a.take<float>((size_t)q_cap * fwd_k),
+          a.take<int>(at_least_one(t_cap) * rev_k), a.take<int>(offs), a.take<int>(offs), a.take<int>(offs),
+          pairs ? a.take<sift_keypoint>((size_t)q_cap) : nullptr,
+          pairs ? a.take<sift_keypoint>(at_least_one(t_cap)) : nullptr, a.take<sift_match>(m),
+          pairs ? a.take<float>(m * 2) : nullptr, pairs ? a.take<float>(m * 2) : nullptr, cross_layout(a, blocks)};
+}
+
+// sift_cross_match_segmented_device: the forward ([q_cap][fwd_k]) and reverse
+// ([t_cap][1]) tables -- rdist only takes the distances the reverse pass writes,
+// nothing reads it -- and the stage's block scan, then the scratch of the
+// forward and of the reverse matcher pass, each that matcher's own device
+// layout (the reverse pass has the capacities exchanged).  The whole block is
+// measured and grown before the first enqueue, so neither pass can move a table
+// under a kernel that is already in the stream.  The two passes' pieces are not
+// aliased (15 pieces at most, the squared-L2 form).
+struct CrossTables { int* idx; float* dist; int* ridx; float* rdist; int* blk_scan; };
+inline CrossTables cross_tables(Carver& a, int q_cap, int fwd_k, int t_cap, int blocks) {
+  return {a.take<int>((size_t)q_cap * fwd_k), a.take<float>((size_t)q_cap * fwd_k), a.take<int>(at_least_one(t_cap)),
+          a.take<float>(at_least_one(t_cap)), cross_layout(a, blocks)};
+}
+template <typename Parts>
+struct CrossMatch { CrossTables tab; Parts fwd, rev; };
+inline CrossMatch<SegParts> cross_match_layout(Carver& a, int n_segments, int q_cap, int t_cap, int fwd_k,
+                                               int fwd_splits, int rev_splits, int blocks) {
+  return {cross_tables(a, q_cap, fwd_k, t_cap, blocks), seg_layout(a, n_segments, q_cap, fwd_splits),
+          seg_layout(a, n_segments, t_cap, rev_splits)};
+}
+inline CrossMatch<SegPartsU8> cross_match_u8_layout(Carver& a, int n_segments, int q_cap, int t_cap, int fwd_k,
+                                                    int fwd_splits, int rev_splits, int blocks) {
+  return {cross_tables(a, q_cap, fwd_k, t_cap, blocks), seg_u8_layout(a, n_segments, q_cap, fwd_splits),
+          seg_u8_layout(a, n_segments, t_cap, rev_splits)};
+}
+inline CrossMatch<SegPartsL2U8> cross_match_l2_u8_layout(Carver& a, int n_segments, int q_cap, int t_cap, int fwd_k,
+                                                         int fwd_splits, int rev_splits, int blocks) {
+  return {cross_tables(a, q_cap, fwd_k, t_cap, blocks), seg_l2_u8_layout(a, n_segments, q_cap, t_cap, fwd_splits),
+          seg_l2_u8_layout(a, n_segments, t_cap, q_cap, rev_splits)};
 }
 
 // sift_bgr8_to_gray: the strided source rows, then the packed gray image.

@@ -37,6 +37,8 @@ SIFT_E_WORKSPACE = -6  # internal candidate workspace overflow: an error, never 
 SIFT_FLAG_FAST, SIFT_FLAG_PROFILE, SIFT_FLAG_VERBOSE, SIFT_FLAG_NO_GRAPH = 0x1, 0x2, 0x4, 0x8
 N_SCALES, N_DOG, DESC_LEN = 5, 4, 128
 HOMOGRAPHY_ROUND = 64  # hypotheses per round of the segmented homography (scratch.hpp kHomogRound)
+# sift_cross_match_segmented_device's metric: the distance and the type of the descriptor rows
+SIFT_METRIC_L1_F32, SIFT_METRIC_L1_U8, SIFT_METRIC_L2SQR_U8 = 0, 1, 2
 
 KEYPOINT_DTYPE = np.dtype(
     [("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
@@ -129,6 +131,12 @@ def lib():
                                                vp]),
             "sift_ratio_matches": (ip, [vp, pint, fp, pint, ip, ip, ctypes.c_double, vp, vp, ip, pint, vp, fp, fp,
                                         ip, pint]),
+            "sift_cross_check_matches_device": (ip, [vp, vp, vp, ip, vp, ip, ip, vp, ip, vp, ip, ctypes.c_double, vp,
+                                                     vp, vp, vp, vp, ip, vp]),
+            "sift_cross_check_matches": (ip, [vp, pint, fp, ip, pint, ip, ip, pint, ip, pint, ip, ctypes.c_double, vp,
+                                              vp, vp, fp, fp, ip, pint]),
+            "sift_cross_match_segmented_device": (ip, [vp, ip, vp, vp, ip, ip, vp, vp, ip, ctypes.c_double, vp, vp,
+                                                       vp, vp, vp, ip, vp]),
             "sift_find_homography_segmented_device": (ip, [vp, vp, vp, vp, ip, ip, ctypes.c_double, ip,
                                                            ctypes.c_double, vp, vp, vp]),
             "sift_find_homography_segmented": (ip, [vp, fp, fp, pint, ip, ip, ctypes.c_double, ip, ctypes.c_double,
@@ -596,6 +604,89 @@ class Context:
                                                     idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _fp(dist)))
         return idx, dist
 
+    # ---- cross-check (mutual nearest neighbours) for a whole batch ------------
+    def cross_check_matches_device(self, idx_ptr: int, dist_ptr: int, fwd_k: int, q_offsets_ptr: int, n_segments: int,
+                                   q_cap: int, ridx_ptr: int, rev_k: int, t_offsets_ptr: int, t_cap: int,
+                                   ratio: float, q_kpts_ptr: int | None, t_kpts_ptr: int | None, matches_ptr: int,
+                                   src_xy_ptr: int | None, dst_xy_ptr: int | None, m_cap: int, m_offsets_ptr: int):
+        """Device-pointer form (no sync) of the cross-check stage: joins a forward
+        result idx / dist [q_cap][fwd_k] with the reverse result ridx [t_cap][rev_k]
+        (the same matcher with query and train exchanged; column 0 is read) into
+        ratio_matches_device's outputs.  Row i of segment b is kept iff train row
+        j = idx[i][0] of the segment's train range has ridx[j][0] == i (local), and,
+        with ratio > 0 (needs fwd_k == 2), it passes the ratio test as well;
+        ratio 0 = cross-check only.  t_offsets_ptr is required."""
+        vp = lambda p: ctypes.c_void_p(p or None)  # noqa: E731
+        self._check("sift_cross_check_matches_device",
+                    self._L.sift_cross_check_matches_device(
+                        self.h, vp(idx_ptr), vp(dist_ptr), fwd_k, vp(q_offsets_ptr), n_segments, q_cap, vp(ridx_ptr),
+                        rev_k, vp(t_offsets_ptr), t_cap, float(ratio), vp(q_kpts_ptr), vp(t_kpts_ptr),
+                        vp(matches_ptr), vp(src_xy_ptr), vp(dst_xy_ptr), m_cap, vp(m_offsets_ptr)))
+
+    def cross_match_segmented_device(self, metric: int, query_ptr: int, q_offsets_ptr: int, n_segments: int,
+                                     q_cap: int, train_ptr: int, t_offsets_ptr: int, t_cap: int, ratio: float,
+                                     q_kpts_ptr: int | None, t_kpts_ptr: int | None, matches_ptr: int,
+                                     src_xy_ptr: int | None, dst_xy_ptr: int | None, m_cap: int, m_offsets_ptr: int):
+        """Device-pointer form (no sync) of the whole job: the forward pass of the
+        metric's segmented matcher (SIFT_METRIC_L1_F32 / _L1_U8 / _L2SQR_U8; k = 2
+        when ratio > 0), the reverse pass and the cross-check stage, the tables in
+        context scratch.  Consecutive frames of a batch: train_ptr = query_ptr,
+        t_offsets_ptr = q_offsets_ptr + 4, t_cap = q_cap, n_segments = batch - 1.
+        With SIFT_METRIC_L2SQR_U8 pass ratio * ratio."""
+        vp = lambda p: ctypes.c_void_p(p or None)  # noqa: E731
+        self._check("sift_cross_match_segmented_device",
+                    self._L.sift_cross_match_segmented_device(
+                        self.h, int(metric), vp(query_ptr), vp(q_offsets_ptr), n_segments, q_cap, vp(train_ptr),
+                        vp(t_offsets_ptr), t_cap, float(ratio), vp(q_kpts_ptr), vp(t_kpts_ptr), vp(matches_ptr),
+                        vp(src_xy_ptr), vp(dst_xy_ptr), m_cap, vp(m_offsets_ptr)))
+
+    def crossCheckMatches(self, idx: np.ndarray, ridx: np.ndarray, q_offsets, t_offsets, dist=None,
+                          ratio: float = 0.0, q_kpts=None, t_kpts=None):
+        """The cross-check stage on host arrays: idx [n_query, k] (and dist, the same
+        shape; zeros when None, which needs ratio 0) from a segmented matcher, ridx
+        [n_train, k'] from the same matcher with the sides exchanged, k and k' 1 or
+        2 (1-D arrays count as k = 1).  Returns ratioMatches' tuple: (matches
+        [MATCH_DTYPE], m_offsets [n_segments + 1], src_xy, dst_xy [n, 2] float32 or
+        None)."""
+        def rows(a, dtype):  # [n] -> [n, 1]; an empty array has no column count of its own
+            a = np.ascontiguousarray(a, dtype)
+            return a.reshape(len(a), -1) if a.size else a.reshape(0, 1)
+        ix, rx = rows(idx, np.int32), rows(ridx, np.int32)
+        if dist is None:
+            if ratio != 0:
+                raise ValueError("the ratio test needs dist")
+            ds = np.zeros(ix.shape, np.float32)
+        else:
+            ds = rows(dist, np.float32)
+        qo = np.ascontiguousarray(q_offsets, np.int32)
+        to = np.ascontiguousarray(t_offsets, np.int32)
+        if ix.shape[1] not in (1, 2) or rx.shape[1] not in (1, 2) or ds.shape != ix.shape:
+            raise ValueError("idx / dist must be [n, 1] or [n, 2] (the same shape) and ridx [m, 1] or [m, 2]")
+        if qo.ndim != 1 or len(qo) < 1 or to.shape != qo.shape:
+            raise ValueError("the offsets must be 1-D, n_segments + 1 entries each")
+        if (q_kpts is None) != (t_kpts is None):
+            raise ValueError("point pairs need both q_kpts and t_kpts")
+        pint = ctypes.POINTER(ctypes.c_int)
+        n = len(ix)
+        matches = np.zeros(n, MATCH_DTYPE)
+        moff = np.zeros(len(qo), np.int32)
+        qk = tk = src = dst = None
+        if q_kpts is not None:
+            qk = np.ascontiguousarray(q_kpts, KEYPOINT_DTYPE)
+            tk = np.ascontiguousarray(t_kpts, KEYPOINT_DTYPE)
+            if len(qk) != n or len(tk) != len(rx):
+                raise ValueError("q_kpts / t_kpts must have one row per query / train row")
+            src, dst = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32)
+        self._check("sift_cross_check_matches",
+                    self._L.sift_cross_check_matches(
+                        self.h, ix.ctypes.data_as(pint), _fp(ds), ix.shape[1], qo.ctypes.data_as(pint), len(qo) - 1, n,
+                        rx.ctypes.data_as(pint), rx.shape[1], to.ctypes.data_as(pint), len(rx), float(ratio),
+                        None if qk is None else qk.ctypes.data, None if tk is None else tk.ctypes.data,
+                        matches.ctypes.data, None if src is None else _fp(src), None if dst is None else _fp(dst),
+                        n, moff.ctypes.data_as(pint)))
+        m = int(moff[-1])
+        return matches[:m], moff, (None if src is None else src[:m]), (None if dst is None else dst[:m])
+
     # ---- a whole batch: homography per segment of the ratio stage's pairs ---
     def find_homography_segmented_device(self, src_xy_ptr: int, dst_xy_ptr: int, m_offsets_ptr: int,
                                          n_segments: int, m_cap: int, H_ptr: int, found_ptr: int,
@@ -904,7 +995,8 @@ class BFMatcher:
     arrays take the byte matcher (integer distances).  NORM_L2SQR: two uint8
     arrays only, DMatch.distance is the squared distance (for a ratio test use
     ratio_test(matches, ratio ** 2)).  NORM_L2 (the square root) is not
-    implemented."""
+    implemented.  crossCheck=True raises: the mutual-nearest-neighbour filter is
+    the module function cross_check_match(query, train, normType)."""
 
     def __init__(self, normType: int = NORM_L1, crossCheck: bool = False, ctx: Context | None = None):
         if normType not in (NORM_L1, NORM_L2SQR) or crossCheck:
@@ -925,6 +1017,29 @@ class BFMatcher:
             idx, dist = ctx.knnMatch(queryDescriptors, trainDescriptors, k)
         return [[DMatch(i, int(idx[i, j]), 0, float(dist[i, j])) for j in range(k) if idx[i, j] >= 0]
                 for i in range(len(idx))]
+
+
+def cross_check_match(query, train, normType: int = NORM_L1, ctx: Context | None = None):
+    """`cv::BFMatcher(normType, crossCheck=True).match(query, train)` for one pair
+    of descriptor sets: the list of DMatch (q, t) where t is q's nearest train row
+    and q is t's nearest query row, in query order; the lower index wins at equal
+    distance in both directions.  The matcher is picked from the dtypes as
+    BFMatcher.knnMatch picks it (NORM_L2SQR: two uint8 arrays, squared distances).
+    Two matcher passes and the cross-check stage (Context.crossCheckMatches)."""
+    both_u8 = np.asarray(query).dtype == np.uint8 and np.asarray(train).dtype == np.uint8
+    if normType not in (NORM_L1, NORM_L2SQR):
+        raise ValueError("only NORM_L1 and NORM_L2SQR are implemented")
+    if normType == NORM_L2SQR and not both_u8:
+        raise ValueError("NORM_L2SQR takes two uint8 descriptor arrays")
+    ctx = ctx or _ctx(1, 1)
+    knn = ctx.knnMatchL2SqrU8Segmented if normType == NORM_L2SQR else \
+        ctx.knnMatchU8Segmented if both_u8 else ctx.knnMatchSegmented
+    q, t = np.asarray(query).reshape(-1, DESC_LEN), np.asarray(train).reshape(-1, DESC_LEN)
+    qo, to = [0, len(q)], [0, len(t)]
+    idx, dist = knn(q, qo, t, to, 1)
+    ridx, _ = knn(t, to, q, qo, 1)
+    m, _, _, _ = ctx.crossCheckMatches(idx, ridx, qo, to, dist)
+    return [DMatch(int(r["query"]), int(r["train"]), 0, float(r["distance"])) for r in m]
 
 
 def ratio_test(matches, ratio: float = 0.86):

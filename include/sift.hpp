@@ -75,6 +75,12 @@ void SITF_BuildIn_OpenCV(InputArray image, std::vector<KeyPoint>& keypoints,
 /* NCL SIFT: the hot path, on the GPU. */
 void SIFT_NCL(InputArray image, std::vector<KeyPoint>& keypoints, OutputArray descriptors);
 
+/* The same with detectAndCompute's mask argument: CV_8UC1, the image's size,
+ * zero = no keypoint here (a keypoint at (x, y) is dropped iff
+ * mask((int)(y + 0.5f), (int)(x + 0.5f)) == 0); applied on the GPU before the
+ * descriptors.  An empty mask is the three-argument call. */
+void SIFT_NCL(InputArray image, InputArray mask, std::vector<KeyPoint>& keypoints, OutputArray descriptors);
+
 /* Sub modules */
 void Gaussian_Blur(Mat& src, Mat& dst, double sigma);
 

@@ -159,6 +159,58 @@ int sift_detect_compute_batch(sift_ctx* ctx, const float* d_imgs, int batch, int
                               size_t row_stride, size_t img_stride, sift_keypoint* d_kpts,
                               float* d_desc, int kp_cap, int* d_img_offsets);
 
+/* ---- detection mask: detectAndCompute(image, mask, ...) ------------------------
+ * The mask argument of OpenCV's feature detectors, applied on the device where
+ * SIFT::detectAndCompute applies it (cv::KeyPointsFilter::runByPixelsMask).  A
+ * mask is rows x cols bytes, the size of the image it belongs to: zero means
+ * "no keypoint here", any other value keeps the keypoint.  A keypoint with
+ * emitted coordinates (x, y) is dropped iff
+ *     mask[(int)(y + 0.5f)][(int)(x + 0.5f)] == 0,
+ * the sums formed in float and truncated toward zero.  An index outside
+ * [0, rows) x [0, cols), or one formed from a NaN coordinate, drops the
+ * keypoint, and no byte outside the mask's rows x cols is ever read (OpenCV
+ * leaves that case undefined; this rule is the library's own).  The orientation
+ * peaks of one extremum share x and y, so they are kept or dropped together.
+ * Order with the keypoint budget: as in OpenCV, retainBest(nfeatures) runs
+ * first and the mask after it.  With sift_set_max_features(n) the cut threshold
+ * is computed over ALL keypoints of the image, masked-out ones included, and
+ * the mask then removes from the survivors -- so an image may end with fewer
+ * than n keypoints although unmasked ones were cut.
+ * The kept keypoints stay in the unmasked order: each image's output is a
+ * subsequence of its unmasked output, and each kept keypoint's 28 bytes and 128
+ * descriptor floats are the unmasked run's bit for bit.  The filter runs before
+ * the emission and the descriptors, so dropped keypoints cost neither.
+ * d_img_offsets, *n_out, the host calls' two-call sizing, sift_copy_results and
+ * every capacity rule (only the first kp_cap rows written, the true total in
+ * d_img_offsets[batch], SIFT_E_CAPACITY from sift_sync) refer to the kept
+ * keypoints: a kp_cap too small for the unmasked total but large enough for
+ * the kept total succeeds.  Exact mode and SIFT_FLAG_FAST, with and without
+ * SIFT_FLAG_NO_GRAPH / _PROFILE / _VERBOSE; not sift_find_scale_space_extrema
+ * (OpenCV filters in detectAndCompute, not there).  A mask of another size
+ * than the image is not supported.
+ *
+ * sift_detect_compute_batch with masks.  d_masks: device bytes, image b's mask
+ * at d_masks + b * mask_img_stride with rows mask_row_stride apart, both in
+ * bytes; mask_img_stride == 0 is one mask shared by every image of the batch.
+ * d_masks == NULL is sift_detect_compute_batch exactly (the mask strides are
+ * ignored, nothing extra is launched); with a mask, mask_row_stride < cols is
+ * SIFT_E_INVALID.  Asynchronous: the masks, like the images, must stay valid
+ * until the stream reaches the call.  In the context's graph cache a masked and
+ * an unmasked call of one shape are two entries, and another mask buffer with
+ * the same strides is an in-place update of the cached executable. */
+int sift_detect_compute_batch_masked(sift_ctx* ctx, const float* d_imgs, int batch, int rows, int cols,
+                                     size_t row_stride, size_t img_stride, const uint8_t* d_masks,
+                                     size_t mask_row_stride, size_t mask_img_stride, sift_keypoint* d_kpts,
+                                     float* d_desc, int kp_cap, int* d_img_offsets);
+/* sift_detect_compute with a host mask (rows mask_row_stride_bytes apart; 0
+ * means cols; less than cols is SIFT_E_INVALID).  mask == NULL is
+ * sift_detect_compute exactly.  The mask is uploaded into a buffer the context
+ * owns (max_rows x max_cols bytes, allocated by the first masked call).
+ * *n_out, the two-call sizing and sift_copy_results report the kept count. */
+int sift_detect_compute_masked(sift_ctx* ctx, const float* img, int rows, int cols, size_t row_stride_bytes,
+                               const uint8_t* mask, size_t mask_row_stride_bytes, sift_keypoint* kpts,
+                               float* desc, int cap, int* n_out);
+
 /* Synthetic integer-exact test images, written on device:
  * image b uses seed 0x5EED0000 + seed_base + b.  Asynchronous. */
 int sift_synth_images(sift_ctx* ctx, float* d_out, int batch, int rows, int cols,
@@ -210,6 +262,16 @@ int sift_multi_set_max_features(sift_multi* m, int n_per_image);
  * offsets (one step behind, so normally without blocking). */
 int sift_multi_step(sift_multi* m, const float* const* d_imgs, const int* counts, int rows, int cols,
                     size_t row_stride, size_t img_stride);
+/* sift_multi_step with detection masks (sift_detect_compute_batch_masked on
+ * every device): d_masks[i] is device i's masks, resident on it, counts[i]
+ * masks mask_img_stride bytes apart (0: one mask for all of that device's
+ * images), rows mask_row_stride bytes apart.  d_masks == NULL, or a NULL entry,
+ * means no mask on that device.  With several streams per device each
+ * sub-batch takes its own slice of the masks.  mask_row_stride < cols with any
+ * mask given is SIFT_E_INVALID, refused before anything is enqueued. */
+int sift_multi_step_masked(sift_multi* m, const float* const* d_imgs, const uint8_t* const* d_masks,
+                           const int* counts, int rows, int cols, size_t row_stride, size_t img_stride,
+                           size_t mask_row_stride, size_t mask_img_stride);
 /* Gathers the last step, drains every stream and reports the contexts' sticky
  * status (as sift_sync).  A step or flush that fails after enqueueing work
  * (a device error, a keypoint count above a context's share of

@@ -106,12 +106,26 @@ void SITF_BuildIn_OpenCV(InputArray image, std::vector<KeyPoint>& keypoints, Out
 
 // src/sift.cpp:59-91
 void SIFT_NCL(InputArray image, std::vector<KeyPoint>& keypoints, OutputArray descriptors) {
+  SIFT_NCL(image, Mat(), keypoints, descriptors);
+}
+
+// detectAndCompute's argument order: the mask (CV_8UC1, the image's size, zero
+// = no keypoint here) is applied on the device; an empty mask is no mask.
+void SIFT_NCL(InputArray image, InputArray mask, std::vector<KeyPoint>& keypoints, OutputArray descriptors) {
   Mat img = image.getMat();
   require_f32(img, "SIFT_NCL");
+  Mat msk = mask.getMat();
+  if (!msk.empty()) {
+    if (msk.type() != CV_8UC1) throw std::runtime_error("SIFT_NCL: expected a CV_8UC1 mask");
+    if (msk.rows != img.rows || msk.cols != img.cols)
+      throw std::runtime_error("SIFT_NCL: the mask must have the image's size");
+    if (!msk.isContinuous()) throw std::runtime_error("SIFT_NCL: expected a continuous mask");
+  }
   sift_ctx* c = ctx_for(img.rows, img.cols);
   int n = 0;
-  int rc = sift_detect_compute(c, img.ptr<float>(0), img.rows, img.cols, sizeof(float) * img.cols,
-                               nullptr, nullptr, 0, &n);
+  int rc = sift_detect_compute_masked(c, img.ptr<float>(0), img.rows, img.cols, sizeof(float) * img.cols,
+                                      msk.empty() ? nullptr : msk.ptr<unsigned char>(0), (size_t)img.cols, nullptr,
+                                      nullptr, 0, &n);
   if (rc != SIFT_OK && rc != SIFT_E_CAPACITY) raise("SIFT_NCL", rc, c);
   keypoints.resize(n);
   descriptors.create(n, SIFT_DESC_LEN, CV_32F);

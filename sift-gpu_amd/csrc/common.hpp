@@ -426,6 +426,20 @@ void launch_emit(hipStream_t st, DetectBufs& D, int batch, sift_keypoint* kpts, 
 // launch per digit pass (one large image) instead of one workgroup per image.
 constexpr int kSelectBins = 256, kSelectPasses = 4;
 void launch_select_best(hipStream_t st, DetectBufs& D, int batch, int n_keep, bool grid_form);
+// detmask.hip: the detection mask of the *_masked entry points
+// (KeyPointsFilter::runByPixelsMask), between launch_select_best and
+// launch_emit.  Not DetectBufs::mask, the candidate bitmask: this is the
+// caller's rows x cols bytes per image, zero = no keypoint here.  Image b's
+// bytes start at bytes + b * img_stride (0: one map for the whole batch), rows
+// are row_stride bytes apart.  npeaks becomes 0 in every live slot whose
+// emitted position rounds (x + 0.5f, y + 0.5f, truncated) to a zero byte or to
+// a pixel outside the image.  bytes == nullptr: nothing is launched.
+// grid_form: launch_select_best's split for one large image.
+struct DetMask {
+  const unsigned char* bytes = nullptr;
+  long long row_stride = 0, img_stride = 0;
+};
+void launch_detmask(hipStream_t st, DetectBufs& D, int batch, const DetMask& dm, int rows, int cols, bool grid_form);
 // Device status bits; bit i <-> sticky error word err[i] (DescArgs::err_flag = &err[0],
 // status_kernel).
 constexpr int kErrAssert = 1;      // keypoint octave/layer outside the pyramid (CV_Assert)

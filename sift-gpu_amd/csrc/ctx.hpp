@@ -59,7 +59,7 @@ class Buf {
   X(ST_RATIO, "ratio_matches") X(ST_HOMOG_SEG, "homography_segmented")                                  \
   X(ST_QUANT_U8, "descriptors_to_u8") X(ST_MATCH_U8, "match_u8_segmented")                               \
   X(ST_MATCH_L2_U8, "match_l2sqr_u8_segmented") X(ST_SELECT, "select_best")                               \
-  X(ST_CROSS, "cross_check_matches")
+  X(ST_CROSS, "cross_check_matches") X(ST_DETMASK, "detect_mask")
 enum Stage {
 #define X(id, name) id,
   SIFT_STAGES(X)
@@ -125,6 +125,10 @@ struct sift_ctx {
   int max_features = 0;
   long long select_block_max = 65536;
   sift::Buf<int> sel_hist;
+  // the detection mask of sift_detect_compute_masked (detmask.hip), uploaded
+  // packed (rows cols bytes apart): max_rows x max_cols bytes, allocated by the
+  // first masked host call and never moved, so captured sequences may name it
+  sift::Buf<unsigned char> d_detmask;
   sift::DetectBufs D{};
   int blk_cap = 0;
   sift::Buf<int> d_img_off;       // [max_batch+1] for the host entry points

@@ -356,21 +356,33 @@ int sift_multi_set_flags(sift_multi* m, unsigned flags) {
   return SIFT_OK;
 }
 
-static int step_impl(sift_multi* m, const float* const* d_imgs, const int* counts, int rows, int cols, size_t row_stride,
-              size_t img_stride);
+static int step_impl(sift_multi* m, const float* const* d_imgs, const uint8_t* const* d_masks, const int* counts,
+                     int rows, int cols, size_t row_stride, size_t img_stride, size_t mask_row_stride,
+                     size_t mask_img_stride);
 static int flush_impl(sift_multi* m);
 
-int sift_multi_step(sift_multi* m, const float* const* d_imgs, const int* counts, int rows, int cols,
-                    size_t row_stride, size_t img_stride) {
+int sift_multi_step_masked(sift_multi* m, const float* const* d_imgs, const uint8_t* const* d_masks, const int* counts,
+                           int rows, int cols, size_t row_stride, size_t img_stride, size_t mask_row_stride,
+                           size_t mask_img_stride) {
   if (!m) return SIFT_E_INVALID;
   if (!m->broken.empty()) return mfail(m, SIFT_E_INVALID, "a previous step failed (" + m->broken + "): destroy the multi context");
   if (!d_imgs || !counts) return mfail(m, SIFT_E_INVALID, "null argument");
-  for (int i = 0; i < m->n; ++i)
+  for (int i = 0; i < m->n; ++i) {
     if (counts[i] < 0 || counts[i] > m->max_batch || (counts[i] > 0 && !d_imgs[i]))
       return mfail(m, SIFT_E_INVALID, "shard " + std::to_string(i) + ": bad image count or null buffer");
-  const int rc = step_impl(m, d_imgs, counts, rows, cols, row_stride, img_stride);
+    // before anything is enqueued: a refused stride leaves the multi context usable
+    if (d_masks && d_masks[i] && cols > 0 && mask_row_stride < (size_t)cols)
+      return mfail(m, SIFT_E_INVALID, "shard " + std::to_string(i) + ": mask_row_stride < cols");
+  }
+  const int rc = step_impl(m, d_imgs, d_masks, counts, rows, cols, row_stride, img_stride, mask_row_stride,
+                           mask_img_stride);
   if (rc) m->broken = m->err;
   return rc;
+}
+
+int sift_multi_step(sift_multi* m, const float* const* d_imgs, const int* counts, int rows, int cols,
+                    size_t row_stride, size_t img_stride) {
+  return sift_multi_step_masked(m, d_imgs, nullptr, counts, rows, cols, row_stride, img_stride, 0, 0);
 }
 
 int sift_multi_flush(sift_multi* m) {
@@ -382,8 +394,9 @@ int sift_multi_flush(sift_multi* m) {
   return rc;
 }
 
-static int step_impl(sift_multi* m, const float* const* d_imgs, const int* counts, int rows, int cols, size_t row_stride,
-              size_t img_stride) {
+static int step_impl(sift_multi* m, const float* const* d_imgs, const uint8_t* const* d_masks, const int* counts,
+                     int rows, int cols, size_t row_stride, size_t img_stride, size_t mask_row_stride,
+                     size_t mask_img_stride) {
   const int s = (int)(m->steps & 1), p = s ^ 1;
   for (int i = 0; i < m->n; ++i)
     for (int j = 0; j < m->S; ++j) {
@@ -395,9 +408,12 @@ static int step_impl(sift_multi* m, const float* const* d_imgs, const int* count
       MHIP(m, hipStreamWaitEvent(cs, m->gdone[s][i], 0));  // step k - 2's gather has read slot s
       m->cnt[s][u] = c;
       if (c > 0) {
-        const int rc = sift_detect_compute_batch(m->ctx[u], d_imgs[i] + (size_t)first * img_stride, c, rows, cols,
-                                                 row_stride, img_stride, m->kbuf[s][u], m->dbuf[s][u], m->cap,
-                                                 m->doff[s][u]);
+        // the sub-batch's own slice of the device's masks (a shared mask, stride 0, is every slice)
+        const uint8_t* dm = d_masks && d_masks[i] ? d_masks[i] + (size_t)first * mask_img_stride : nullptr;
+        const int rc = sift_detect_compute_batch_masked(m->ctx[u], d_imgs[i] + (size_t)first * img_stride, c, rows,
+                                                        cols, row_stride, img_stride, dm, mask_row_stride,
+                                                        mask_img_stride, m->kbuf[s][u], m->dbuf[s][u], m->cap,
+                                                        m->doff[s][u]);
         if (rc) return mfail(m, rc, "device " + std::to_string(m->dev[i]) + ": " + sift_last_error(m->ctx[u]));
         MHIP(m, hipMemcpyAsync(m->hoff[s][u], m->doff[s][u], sizeof(int) * (size_t)(c + 1), hipMemcpyDeviceToHost,
                                cs));

@@ -160,8 +160,12 @@ void enqueue_pyramid(sift_ctx* c, const Layout& L, Plane src, int batch, bool wi
 // keypoints by response, ties at the cut included (select.hip), before the
 // scan -- so the offsets, the emitted list and the descriptor work are the
 // kept keypoints'.
+// dm.bytes != nullptr (the *_masked calls only): after the budget, as OpenCV
+// orders retainBest and runByPixelsMask, every keypoint on a zero byte of the
+// image's detection mask is dropped as well (detmask.hip).
 void enqueue_detect(sift_ctx* c, const Layout& L, int batch, sift_keypoint* kpts, int kp_cap,
-                    int* img_off, bool dog_from_gpyr, unsigned sparse = 0, int max_features = 0) {
+                    int* img_off, bool dog_from_gpyr, unsigned sparse = 0, int max_features = 0,
+                    const DetMask& dm = DetMask{}) {
   hipStream_t st = c->stream;
   {
     StageScope s(c, ST_EXTREMA);
@@ -176,6 +180,10 @@ void enqueue_detect(sift_ctx* c, const Layout& L, int batch, sift_keypoint* kpts
   if (max_features > 0) {
     StageScope s(c, ST_SELECT);
     launch_select_best(st, c->D, batch, max_features, c->D.cand_cap / c->max_batch > c->select_block_max);
+  }
+  if (dm.bytes) {
+    StageScope s(c, ST_DETMASK);
+    launch_detmask(st, c->D, batch, dm, L.rows, L.cols, c->D.cand_cap / c->max_batch > c->select_block_max);
   }
   {
     StageScope s(c, ST_EMIT);
@@ -230,7 +238,8 @@ void verbose_phase(sift_ctx* c, const char* what, hipEvent_t a, hipEvent_t b) {
 // SIFT_FLAG_VERBOSE launches it directly with an event between the phases
 // and prints the reference's three timing lines.
 int enqueue_ncl(sift_ctx* c, const float* d_imgs, int batch, int rows, int cols, size_t row_stride,
-                size_t img_stride, sift_keypoint* d_kpts, float* d_desc, int kp_cap, int* d_img_offsets) {
+                size_t img_stride, sift_keypoint* d_kpts, float* d_desc, int kp_cap, int* d_img_offsets,
+                const DetMask& dm = DetMask{}) {
   const Layout L = make_layout(rows, cols, c->n_oct);
   const Plane src{d_imgs, (long long)row_stride, (long long)img_stride};
   if (int rc = check_fast(c, L, (long long)row_stride)) return rc;
@@ -249,7 +258,7 @@ int enqueue_ncl(sift_ctx* c, const float* d_imgs, int batch, int rows, int cols,
     mark(0);
     enqueue_pyramid(c, L, src, batch, false, sparse);
     mark(1);
-    enqueue_detect(c, L, batch, d_kpts, kp_cap, d_img_offsets, true, sparse, c->max_features);
+    enqueue_detect(c, L, batch, d_kpts, kp_cap, d_img_offsets, true, sparse, c->max_features, dm);
     mark(2);
     enqueue_desc(c, L, d_kpts, d_img_offsets, batch, kp_cap, d_desc, 0, true);
     mark(3);
@@ -268,8 +277,8 @@ int enqueue_ncl(sift_ctx* c, const float* d_imgs, int batch, int rows, int cols,
   // sequence id 1, then everything that shapes the sequence; stall_once is the
   // test hook: a captured poll bound must not be replayed
   key_put(key, 1, batch, rows, cols, row_stride, img_stride, kp_cap, c->n_oct, c->flags, c->stall_once, sparse,
-          c->max_features);
-  key_put(ptrs, d_imgs, d_kpts, d_desc, d_img_offsets);
+          c->max_features, dm.bytes != nullptr, dm.row_stride, dm.img_stride);
+  key_put(ptrs, d_imgs, dm.bytes, d_kpts, d_desc, d_img_offsets);
   return run_graphed(c, key, ptrs, body);
 }
 
@@ -386,35 +395,70 @@ int sift_copy_results(sift_ctx* c, sift_keypoint* kpts, float* desc, int cap, in
   return SIFT_OK;
 }
 
-int sift_detect_compute_batch(sift_ctx* c, const float* d_imgs, int batch, int rows, int cols,
-                              size_t row_stride, size_t img_stride, sift_keypoint* d_kpts,
-                              float* d_desc, int kp_cap, int* d_img_offsets) {
+int sift_detect_compute_batch_masked(sift_ctx* c, const float* d_imgs, int batch, int rows, int cols,
+                                     size_t row_stride, size_t img_stride, const uint8_t* d_masks,
+                                     size_t mask_row_stride, size_t mask_img_stride, sift_keypoint* d_kpts,
+                                     float* d_desc, int kp_cap, int* d_img_offsets) {
   if (!c) return SIFT_E_INVALID;
   int rc = check_dims(c, rows, cols, c->n_oct, batch);
   if (rc) return rc;
   if (!d_imgs || !d_kpts || !d_desc || !d_img_offsets || kp_cap < 0 || row_stride < (size_t)cols)
     return fail(c, SIFT_E_INVALID, "null buffer or bad stride");
+  if (d_masks && mask_row_stride < (size_t)cols) return fail(c, SIFT_E_INVALID, "mask_row_stride < cols");
   (void)hipSetDevice(c->device);
   c->last_n = -1;
+  // without a mask its strides shape nothing: one cached sequence whatever they are
+  const DetMask dm = d_masks ? DetMask{d_masks, (long long)mask_row_stride, (long long)mask_img_stride} : DetMask{};
   return enqueue_ncl(c, d_imgs, batch, rows, cols, row_stride, img_stride, d_kpts, d_desc, kp_cap,
-                     d_img_offsets);
+                     d_img_offsets, dm);
+}
+
+int sift_detect_compute_batch(sift_ctx* c, const float* d_imgs, int batch, int rows, int cols,
+                              size_t row_stride, size_t img_stride, sift_keypoint* d_kpts,
+                              float* d_desc, int kp_cap, int* d_img_offsets) {
+  return sift_detect_compute_batch_masked(c, d_imgs, batch, rows, cols, row_stride, img_stride, nullptr, 0, 0, d_kpts,
+                                          d_desc, kp_cap, d_img_offsets);
 }
 
 // SIFT_NCL from host memory: upload -> the graphed device sequence -> the
 // host-detection tail above.
-int sift_detect_compute(sift_ctx* c, const float* img, int rows, int cols, size_t row_stride_bytes,
-                        sift_keypoint* kpts, float* desc, int cap, int* n_out) {
+// With a mask: it is uploaded once, packed, into the context's own buffer
+// beside the image; the grow-and-run-again path of host_detect enqueues the
+// sequence again on that uploaded copy.
+int sift_detect_compute_masked(sift_ctx* c, const float* img, int rows, int cols, size_t row_stride_bytes,
+                               const uint8_t* mask, size_t mask_row_stride_bytes, sift_keypoint* kpts, float* desc,
+                               int cap, int* n_out) {
   if (!c) return SIFT_E_INVALID;
   if (!img || !n_out) return fail(c, SIFT_E_INVALID, "null image or n_out");
   if (row_stride_bytes == 0) row_stride_bytes = (size_t)cols * sizeof(float);
+  if (mask_row_stride_bytes == 0) mask_row_stride_bytes = (size_t)(cols > 0 ? cols : 0);
   if (int rc = check_dims(c, rows, cols, c->n_oct, 1)) return rc;
+  if (mask && mask_row_stride_bytes < (size_t)cols) return fail(c, SIFT_E_INVALID, "mask_row_stride_bytes < cols");
   (void)hipSetDevice(c->device);
+  if (mask && !c->d_detmask.get() &&
+      c->d_detmask.grow((size_t)c->max_rows * c->max_cols) != hipSuccess)
+    return fail(c, SIFT_E_NOMEM, "detection mask buffer");
+  const DetMask dm = mask ? DetMask{c->d_detmask, cols, 0} : DetMask{};
   return host_detect(
-      c, true, kpts, desc, cap, n_out, [&] { return upload_image(c, img, rows, cols, row_stride_bytes); },
+      c, true, kpts, desc, cap, n_out,
+      [&]() -> int {
+        if (int rc = upload_image(c, img, rows, cols, row_stride_bytes)) return rc;
+        if (mask) {
+          StageScope s(c, ST_UPLOAD, 0, 1.0 * rows * cols);
+          HIP_TRY(c, hipMemcpy2DAsync(c->d_detmask, (size_t)cols, mask, mask_row_stride_bytes, (size_t)cols, rows,
+                                      hipMemcpyHostToDevice, c->stream));
+        }
+        return SIFT_OK;
+      },
       [&] {
         return enqueue_ncl(c, c->d_in, 1, rows, cols, c->in_pitch, c->in_img, c->d_kpts, c->d_desc, c->kp_cap,
-                           c->d_img_off);
+                           c->d_img_off, dm);
       });
+}
+
+int sift_detect_compute(sift_ctx* c, const float* img, int rows, int cols, size_t row_stride_bytes,
+                        sift_keypoint* kpts, float* desc, int cap, int* n_out) {
+  return sift_detect_compute_masked(c, img, rows, cols, row_stride_bytes, nullptr, 0, kpts, desc, cap, n_out);
 }
 
 int sift_gaussian_blur(sift_ctx* c, const float* src, int rows, int cols, double sigma, float* dst) {

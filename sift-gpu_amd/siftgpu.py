@@ -98,6 +98,8 @@ def lib():
             "sift_packed_size": (sz, [ip, ip, ip, ip]),
             "sift_detect_compute": (ip, [vp, fp, ip, ip, sz, vp, fp, ip, pint]),
             "sift_detect_compute_batch": (ip, [vp, vp, ip, ip, ip, sz, sz, vp, vp, ip, vp]),
+            "sift_detect_compute_masked": (ip, [vp, fp, ip, ip, sz, vp, sz, vp, fp, ip, pint]),
+            "sift_detect_compute_batch_masked": (ip, [vp, vp, ip, ip, ip, sz, sz, vp, sz, sz, vp, vp, ip, vp]),
             "sift_copy_results": (ip, [vp, vp, fp, ip, pint]),
             "sift_synth_images": (ip, [vp, vp, ip, ip, ip, sz, sz, ip]),
             "sift_gaussian_blur": (ip, [vp, fp, ip, ip, ctypes.c_double, fp]),
@@ -152,6 +154,8 @@ def lib():
             "sift_multi_last_error": (ctypes.c_char_p, [vp]),
             "sift_multi_context": (vp, [vp, ip]),
             "sift_multi_step": (ip, [vp, ctypes.POINTER(vp), pint, ip, ip, sz, sz]),
+            "sift_multi_step_masked": (ip, [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), pint, ip, ip, sz, sz, sz,
+                                            sz]),
             "sift_multi_flush": (ip, [vp]),
             "sift_multi_gathered": (ip, [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), pint, ip, pint,
                                          ctypes.POINTER(ctypes.c_longlong)]),
@@ -161,7 +165,8 @@ def lib():
             "sift_multi_copy_gathered": (ip, [vp, vp, fp, ip, pint]),
         }
         optional = {"sift_graph_stats", "sift_g4_fill_stats", "sift_set_max_features",
-                    "sift_multi_set_max_features"}  # absent from older builds (A/B runs against a saved library)
+                    "sift_multi_set_max_features", "sift_detect_compute_masked", "sift_detect_compute_batch_masked",
+                    "sift_multi_step_masked"}  # absent from older builds (A/B runs against a saved library)
         for name, (res, args) in sigs.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -175,6 +180,20 @@ def lib():
 def _fp(a: np.ndarray):
     assert a.dtype == np.float32 and a.flags.c_contiguous
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
+def _detection_mask(mask, shape):
+    """The detection mask of SIFT_NCL as packed uint8 (None stays None): a uint8 or
+    bool array of the image's shape, zero / False = no keypoint here.  Anything
+    else raises ValueError -- before any library call."""
+    if mask is None:
+        return None
+    m = np.asarray(mask)
+    if m.dtype != np.uint8 and m.dtype != np.bool_:
+        raise ValueError(f"mask must be uint8 or bool, not {m.dtype}")
+    if m.shape != tuple(shape):
+        raise ValueError(f"mask has shape {m.shape}, the image has {tuple(shape)}")
+    return np.ascontiguousarray(m).view(np.uint8)
 
 
 def octave_shapes(rows: int, cols: int, n_octaves: int = 5):
@@ -279,11 +298,15 @@ class Context:
         self._check("sift_set_max_features", self._L.sift_set_max_features(self.h, n))
 
     # ---- host-memory API (reference names) ------------------------------
-    def SIFT_NCL(self, img: np.ndarray, row_stride_bytes: int | None = None):
+    def SIFT_NCL(self, img: np.ndarray, row_stride_bytes: int | None = None, mask=None):
         """row_stride_bytes None: img is copied to a contiguous float32 array.
         A number: img's own memory is passed with that row stride (img must be
         2-D float32 with unit column stride and rows that many bytes apart;
-        0 is the ABI's default, cols * 4)."""
+        0 is the ABI's default, cols * 4).
+        mask: detectAndCompute's mask, a uint8 or bool array of the image's shape;
+        a keypoint at (x, y) is dropped iff mask[int(y + 0.5), int(x + 0.5)] == 0
+        (on the device, before the descriptors; include/sift_hip.h)."""
+        mask = _detection_mask(mask, np.shape(img))
         if row_stride_bytes is None:
             img = np.ascontiguousarray(img, np.float32)
             row_stride_bytes = img.shape[1] * 4
@@ -292,8 +315,13 @@ class Context:
             raise ValueError("img must be a 2-D float32 view whose rows are row_stride_bytes apart")
         r, c = img.shape
         n = ctypes.c_int(0)
-        rc = self._L.sift_detect_compute(self.h, img.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), r, c,
-                                         row_stride_bytes, None, None, 0, ctypes.byref(n))
+        if mask is None:
+            rc = self._L.sift_detect_compute(self.h, img.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), r, c,
+                                             row_stride_bytes, None, None, 0, ctypes.byref(n))
+        else:
+            rc = self._L.sift_detect_compute_masked(self.h, img.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), r, c,
+                                                    row_stride_bytes, mask.ctypes.data, c, None, None, 0,
+                                                    ctypes.byref(n))
         if rc not in (SIFT_OK, SIFT_E_CAPACITY):
             self._check("sift_detect_compute", rc)
         kps = np.zeros(n.value, KEYPOINT_DTYPE)
@@ -744,12 +772,23 @@ class Context:
                                               row_stride, img_stride, seed_base))
 
     def detect_compute_batch(self, imgs_ptr: int, batch: int, rows: int, cols: int, row_stride: int,
-                             img_stride: int, kpts_ptr: int, desc_ptr: int, kp_cap: int, offs_ptr: int):
-        self._check("sift_detect_compute_batch",
-                    self._L.sift_detect_compute_batch(self.h, ctypes.c_void_p(imgs_ptr), batch, rows, cols,
-                                                      row_stride, img_stride, ctypes.c_void_p(kpts_ptr),
-                                                      ctypes.c_void_p(desc_ptr), kp_cap,
-                                                      ctypes.c_void_p(offs_ptr)))
+                             img_stride: int, kpts_ptr: int, desc_ptr: int, kp_cap: int, offs_ptr: int,
+                             masks_ptr: int = 0, mask_row_stride: int = 0, mask_img_stride: int = 0):
+        """masks_ptr: device uint8 detection masks, image b's at masks_ptr + b * mask_img_stride with rows
+        mask_row_stride bytes apart (mask_img_stride 0: one mask for the whole batch); 0 = no mask."""
+        if not masks_ptr:
+            self._check("sift_detect_compute_batch",
+                        self._L.sift_detect_compute_batch(self.h, ctypes.c_void_p(imgs_ptr), batch, rows, cols,
+                                                          row_stride, img_stride, ctypes.c_void_p(kpts_ptr),
+                                                          ctypes.c_void_p(desc_ptr), kp_cap,
+                                                          ctypes.c_void_p(offs_ptr)))
+            return
+        self._check("sift_detect_compute_batch_masked",
+                    self._L.sift_detect_compute_batch_masked(self.h, ctypes.c_void_p(imgs_ptr), batch, rows, cols,
+                                                             row_stride, img_stride, ctypes.c_void_p(masks_ptr),
+                                                             mask_row_stride, mask_img_stride,
+                                                             ctypes.c_void_p(kpts_ptr), ctypes.c_void_p(desc_ptr),
+                                                             kp_cap, ctypes.c_void_p(offs_ptr)))
 
     def selftest_math(self, op: int, a: np.ndarray, b: np.ndarray | None = None) -> np.ndarray:
         """One device helper element-wise (sift_hip.h lists ops 0..7); ops 8 / 9 are the
@@ -862,11 +901,23 @@ class MultiContext:
                                        rows, cols, row_stride, img_stride, seed_base)
         self._check("sift_synth_images", rc)
 
-    def step(self, img_ptrs, counts, rows: int, cols: int, row_stride: int, img_stride: int):
+    def step(self, img_ptrs, counts, rows: int, cols: int, row_stride: int, img_stride: int, mask_ptrs=None,
+             mask_row_stride: int = 0, mask_img_stride: int = 0):
+        """mask_ptrs: per device, a pointer to its uint8 detection masks (strides in bytes as in
+        Context.detect_compute_batch) or 0 / None for no mask on that device; None = no masks."""
         n = len(self.devices)
         ptrs = (ctypes.c_void_p * n)(*[ctypes.c_void_p(p) for p in img_ptrs])
         cnt = (ctypes.c_int * n)(*counts)
-        self._check("sift_multi_step", self._L.sift_multi_step(self.h, ptrs, cnt, rows, cols, row_stride, img_stride))
+        if mask_ptrs is None:
+            self._check("sift_multi_step",
+                        self._L.sift_multi_step(self.h, ptrs, cnt, rows, cols, row_stride, img_stride))
+            return
+        if len(mask_ptrs) != n:
+            raise ValueError("mask_ptrs needs one entry per device")
+        mptrs = (ctypes.c_void_p * n)(*[ctypes.c_void_p(p or None) for p in mask_ptrs])
+        self._check("sift_multi_step_masked",
+                    self._L.sift_multi_step_masked(self.h, ptrs, mptrs, cnt, rows, cols, row_stride, img_stride,
+                                                   mask_row_stride, mask_img_stride))
 
     def flush(self):
         self._check("sift_multi_flush", self._L.sift_multi_flush(self.h))
@@ -923,8 +974,10 @@ def _ctx(rows, cols):
     return _default
 
 
-def SIFT_NCL(image):
-    return _ctx(*image.shape).SIFT_NCL(image)
+def SIFT_NCL(image, mask=None):
+    """mask: detectAndCompute's mask (uint8 or bool, the image's shape; zero = no keypoint here)."""
+    mask = _detection_mask(mask, np.shape(image))
+    return _ctx(*image.shape).SIFT_NCL(image, mask=mask)
 
 
 def Gaussian_Blur(src, sigma):

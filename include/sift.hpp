@@ -81,6 +81,15 @@ void SIFT_NCL(InputArray image, std::vector<KeyPoint>& keypoints, OutputArray de
  * descriptors.  An empty mask is the three-argument call. */
 void SIFT_NCL(InputArray image, InputArray mask, std::vector<KeyPoint>& keypoints, OutputArray descriptors);
 
+/* detectAndCompute's full argument list.  useProvidedKeypoints false: the call
+ * above.  true: nothing is detected; `keypoints` are described unchanged
+ * (Feature2D::compute) in the pyramid SIFT_NCL builds for the image, and the
+ * mask is ignored, as OpenCV ignores it.  OpenCV upsamples the image when a
+ * keypoint has a negative octave; the reference never does, so such a keypoint
+ * (or one whose octave or layer is outside the pyramid) makes the call throw. */
+void SIFT_NCL(InputArray image, InputArray mask, std::vector<KeyPoint>& keypoints, OutputArray descriptors,
+              bool useProvidedKeypoints);
+
 /* Sub modules */
 void Gaussian_Blur(Mat& src, Mat& dst, double sigma);
 

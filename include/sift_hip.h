@@ -211,6 +211,57 @@ int sift_detect_compute_masked(sift_ctx* ctx, const float* img, int rows, int co
                                const uint8_t* mask, size_t mask_row_stride_bytes, sift_keypoint* kpts,
                                float* desc, int cap, int* n_out);
 
+/* ---- provided keypoints: detectAndCompute(..., useProvidedKeypoints = true) ------
+ * OpenCV's Feature2D::compute(): describe images at keypoints the caller already
+ * holds -- the keypoints of the previous frame carried into this one, a dense
+ * grid, another detector's points.  Nothing is detected and no keypoint field is
+ * changed (the orientation is taken as given, as OpenCV takes it).
+ *
+ * sift_compute_batch.  Images as for sift_detect_compute_batch.  d_kpts: kp_cap
+ * rows, only read.  d_desc: kp_cap x 128 floats.  d_kp_offsets: batch + 1 device
+ * ints, exactly what sift_detect_compute_batch leaves in d_img_offsets: image b
+ * owns rows [clamp(off[b]), clamp(off[b+1])), every bound clamped to
+ * [0, kp_cap]; empty images are allowed, and descriptor rows before
+ * clamp(off[0]) or at and past clamp(off[batch]) are never written.
+ * Row k's 128 floats are calDescriptor (src/sift.cpp:733-753) of keypoint k in
+ * the pyramid SIFT_NCL builds for its image (the context's octave count,
+ * firstOctave 0): in exact mode, bit for bit what sift_build_gaussian_pyramid +
+ * sift_calc_descriptors(..., first_octave = 0) give, and for keypoints that
+ * sift_detect_compute_batch emitted on the same images, the descriptors that
+ * call wrote (under SIFT_FLAG_FAST too, on the fast pyramid).  Angles follow
+ * sift_calc_descriptors' contract (the bin wraps modulo 8).
+ * firstOctave: OpenCV derives it from the keypoints and upsamples the image for
+ * a negative octave; the reference never upsamples, so here the pyramid starts
+ * at octave 0 and a row with a negative octave is an invalid row.
+ * max_layer, 0 .. 4 (else SIFT_E_INVALID), is the caller's promise that no row
+ * names a scale above it: only scales 0 .. max_layer are differentiated, and
+ * with max_layer <= 3 the widest blur (w = 18) is not computed where the blur
+ * form in use can leave it out.  4 admits every scale the reference allows; 3
+ * covers every keypoint a SIFT detection emits.
+ * Invalid rows: octave < 0, octave >= the context's octave count, layer > 4 or
+ * layer > max_layer.  Such a row gets 128 zeros and sets the sticky assertion
+ * bit, which sift_sync reports as SIFT_E_INVALID once; other rows are not
+ * affected.
+ * Asynchronous on the context stream: no synchronisation and no host read of an
+ * offset (the ranking scratch grows, with a wait, only for a kp_cap above every
+ * earlier call's).  In the graph cache the sequence has its own entries, keyed
+ * by the shape, kp_cap, the octave count, the flags and max_layer; other
+ * buffers of the same shape update the cached executable in place.  Under
+ * SIFT_FLAG_PROFILE its stages are the pyramid's, "gradient", "compute_prep" and
+ * "descriptor".  The keypoint budget and the detection masks do not apply.
+ * batch == 0 or kp_cap == 0: SIFT_OK, nothing is enqueued.  kp_cap above 2^30 is
+ * SIFT_E_SIZE. */
+int sift_compute_batch(sift_ctx* ctx, const float* d_imgs, int batch, int rows, int cols, size_t row_stride,
+                       size_t img_stride, const sift_keypoint* d_kpts, const int* d_kp_offsets, int kp_cap,
+                       int max_layer, float* d_desc);
+/* The same from host memory, synchronous: one image (rows row_stride_bytes
+ * apart, 0 = cols * 4), n keypoints in, n x 128 floats out.  SIFT_E_INVALID if
+ * any row was invalid -- the n rows are written all the same, the invalid ones
+ * as zeros.  n == 0 is SIFT_OK.  Like sift_calc_descriptors it uses the
+ * context's keypoint buffer, so sift_copy_results has nothing to copy after it. */
+int sift_compute(sift_ctx* ctx, const float* img, int rows, int cols, size_t row_stride_bytes,
+                 const sift_keypoint* kpts, int n, int max_layer, float* desc);
+
 /* Synthetic integer-exact test images, written on device:
  * image b uses seed 0x5EED0000 + seed_base + b.  Asynchronous. */
 int sift_synth_images(sift_ctx* ctx, float* d_out, int batch, int rows, int cols,

@@ -136,6 +136,26 @@ void SIFT_NCL(InputArray image, InputArray mask, std::vector<KeyPoint>& keypoint
   }
 }
 
+// detectAndCompute(image, mask, keypoints, descriptors, useProvidedKeypoints)
+void SIFT_NCL(InputArray image, InputArray mask, std::vector<KeyPoint>& keypoints, OutputArray descriptors,
+              bool useProvidedKeypoints) {
+  if (!useProvidedKeypoints) {
+    SIFT_NCL(image, mask, keypoints, descriptors);
+    return;
+  }
+  Mat img = image.getMat();
+  require_f32(img, "SIFT_NCL");
+  const int n = (int)keypoints.size();
+  descriptors.create(n, SIFT_DESC_LEN, CV_32F);
+  if (n == 0) return;
+  Mat d = descriptors.getMat();
+  sift_ctx* c = ctx_for(img.rows, img.cols);
+  int rc = sift_compute(c, img.ptr<float>(0), img.rows, img.cols, sizeof(float) * img.cols,
+                        reinterpret_cast<const sift_keypoint*>(keypoints.data()), n, SIFT_N_SCALES - 1,
+                        d.ptr<float>(0));
+  if (rc) raise("SIFT_NCL", rc, c);
+}
+
 // src/sift.cpp:123-153
 void Gaussian_Blur(Mat& src, Mat& dst, double sigma) {
   require_f32(src, "Gaussian_Blur");

@@ -455,6 +455,30 @@ void launch_descriptors(hipStream_t st, const Layout& L, const float2* grad, con
                         int kp_cap, float* desc, int first_octave, int* err_flag,
                         bool detected,  // detected: keypoints from this library's detection (radius <= 40)
                         int* perm);     // [kp_cap] scratch: the lane-balance ranking
+// compute.hip (sift_compute_batch: descriptors at keypoints the caller holds).
+// The prep pass over rows [clamp(off[0]), clamp(off[batch])) of kpts, every
+// offset clamped to [0, kp_cap] (match_seg.hpp): a row with oi < 0,
+// oi >= L.n_oct, layer > 4 or layer > max_layer gets 128 zeros in desc and
+// sets err_flag (kErrAssert); every other row goes into one of two index
+// lists -- det: the rows descriptor_kernel's detected-keypoint form can take
+// (window radius <= 40 and the keypoint's pixel inside the octave's interior),
+// gen: the rest -- ranked by window size within each run of kComputeChunk
+// consecutive rows, as desc_rank_kernel ranks.  det and gen hold kp_cap ints
+// each; counts[0], counts[1] are their lengths (the launch clears them first).
+// The order of the runs within a list varies from call to call; it affects
+// speed only.
+constexpr int kComputeChunk = 256;
+struct DescLists {
+  int* det;
+  int* gen;
+  int* counts;  // [2]
+};
+void launch_compute_prep(hipStream_t st, const Layout& L, const sift_keypoint* kpts, const int* off, int batch,
+                         int kp_cap, int max_layer, float* desc, int* err_flag, const DescLists& lists);
+// descriptor.hip: the two descriptor launches over those lists (first_octave 0)
+void launch_descriptors_listed(hipStream_t st, const Layout& L, const float2* grad, const MathConsts* mc,
+                               const sift_keypoint* kpts, const int* img_kp_off, int batch, int kp_cap, float* desc,
+                               int* err_flag, const DescLists& lists);
 void launch_math_selftest(hipStream_t st, int op, const float* a, const float* b, float* out, int n,
                           const MathConsts* mc);
 

@@ -76,6 +76,11 @@ struct DescArgs {
   float* desc;
   int first_octave;
   int* err_flag;
+  // Optional (descriptor_kernel<..., LIST = true> only; compute.hip's prep
+  // kernel writes them): the launch describes rows list[0 .. *list_n) of kpts
+  // in that order, instead of every row below img_kp_off[batch].
+  const int* list = nullptr;
+  const int* list_n = nullptr;
 };
 
 // Narrow [lo, hi] to the j with |j*a + b| < 2.5 (+ margin).
@@ -133,11 +138,16 @@ struct RecT {  // one lane's 8 corner records
 // PARTS = 4 (one image, round 6; 2 and 8 for A/B builds): a keypoint's window
 // is split over PARTS groups of one wave by the part of the interior rows (and
 // columns) its bins lie in; see "Window parts" below.
-template <bool DET, int PF, int WPE, int PARTS = 1>
+// LIST (sift_compute_batch): the rows to describe are A.list[0 .. *A.list_n),
+// already ranked by window size, instead of rows 0 .. img_kp_off[batch); the
+// caller vouches for DET's preconditions row by row (compute_prep_kernel).
+template <bool DET, int PF, int WPE, int PARTS = 1, bool LIST = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void
 descriptor_kernel(DescArgs A) {
   static_assert(PF == 1 || PF == 2, "one or two sample batches in flight");
   static_assert(PARTS == 1 || ((PARTS == 2 || PARTS == 4 || PARTS == 8) && DET), "window parts: detected keypoints (row table) only");
+  static_assert(!LIST || PARTS == 1, "row lists: whole windows only");
+  constexpr int kNoRow = 0x7fffffff;  // LIST: a sub-batch slot past the list's end
   constexpr int kKpw = kGrp / PARTS;  // keypoints per wave
   // [qidx][group*8 + parity]
   constexpr int kHistRows = kQBins;
@@ -154,7 +164,7 @@ descriptor_kernel(DescArgs A) {
   const int lane = threadIdx.x & 63;
   const int g = lane >> 3, q = lane & 7;
   const int d = kDescW, nb = kDescBins;
-  int n = A.img_kp_off[A.batch];
+  int n = LIST ? *A.list_n : A.img_kp_off[A.batch];
   if (n > A.kp_cap) n = A.kp_cap;
   const ExpConsts ek = A.mc->e;
   const float etab_lane = A.mc->exptab[lane];  // lane j holds 2^(j/64) * A0 (exp32f_v)
@@ -199,7 +209,11 @@ descriptor_kernel(DescArgs A) {
       const int ch = sb / kSubPerChunk;
       const int pos = (sb % kSubPerChunk) ^ (int)(((unsigned)ch * 0x9E3779B1u) >> (32 - kSubBits));
       const int i = k0 + ch * kRankChunk + pos * kGrp + lane;
-      if (lane < kGrp) sord[lane] = i < kend ? (A.perm ? A.perm[i] : i) : kend;
+      if constexpr (LIST) {
+        if (lane < kGrp) sord[lane] = i < kend ? A.list[i] : kNoRow;
+      } else {
+        if (lane < kGrp) sord[lane] = i < kend ? (A.perm ? A.perm[i] : i) : kend;
+      }
       wave_sync_d();
     }
     const int kslot = g / PARTS;            // this group's keypoint among the wave's kKpw
@@ -222,7 +236,7 @@ descriptor_kernel(DescArgs A) {
     const float rlim_hi = PARTS == 8 ? rq - 0.5f : PARTS > 1 ? 2.f * hr + 0.5f : 2.5f;
     const float clim_lo = PARTS >= 4 ? 2.f * hc - 2.5f : -2.5f, clim_hi = PARTS >= 4 ? 2.f * hc + 0.5f : 2.5f;
     const int k = sord[kslot];
-    bool active = k < kend;
+    bool active = LIST ? k != kNoRow : k < kend;
     int b = 0, oi = 0, layer = 0;
     sift_keypoint kp{};
     if (active) {
@@ -919,6 +933,40 @@ void launch_descriptors(hipStream_t st, const Layout& L, const float2* grad, con
   else
     SIFT_DESC_LAUNCH(false, 1, kDescWpe);
 #undef SIFT_DESC_LAUNCH
+}
+
+// sift_compute_batch: two launches over the row lists of launch_compute_prep,
+// each sized from its device-resident count -- the detected-keypoint form
+// (row table, two batches in flight) over the rows that meet its
+// preconditions, the general whole-window form over the rest.  Whole windows
+// and resident grids for any batch, one image included: a caller's rows are
+// not in layer order, and an empty list costs one launch of waves that exit.
+void launch_descriptors_listed(hipStream_t st, const Layout& L, const float2* grad, const MathConsts* mc,
+                               const sift_keypoint* kpts, const int* img_kp_off, int batch, int kp_cap, float* desc,
+                               int* err_flag, const DescLists& lists) {
+  if (kp_cap <= 0) return;
+  DescArgs A;
+  A.L = L;
+  A.grad = grad;
+  A.mc = mc;
+  A.kpts = kpts;
+  A.perm = nullptr;
+  A.img_kp_off = img_kp_off;
+  A.batch = batch;
+  A.kp_cap = kp_cap;
+  A.desc = desc;
+  A.first_octave = 0;
+  A.err_flag = err_flag;
+  A.list = lists.det;
+  A.list_n = lists.counts;
+  hipLaunchKernelGGL((descriptor_kernel<true, 2, kDescWpe, 1, true>),
+                     dim3(std::max(8, resident_grid((const void*)descriptor_kernel<true, 2, kDescWpe, 1, true>, 64, 0, 8192))),
+                     dim3(64), 0, st, A);
+  A.list = lists.gen;
+  A.list_n = lists.counts + 1;
+  hipLaunchKernelGGL((descriptor_kernel<false, 1, kDescWpe, 1, true>),
+                     dim3(std::max(8, resident_grid((const void*)descriptor_kernel<false, 1, kDescWpe, 1, true>, 64, 0, 8192))),
+                     dim3(64), 0, st, A);
 }
 
 }  // namespace sift

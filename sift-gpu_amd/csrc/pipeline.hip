@@ -282,6 +282,52 @@ int enqueue_ncl(sift_ctx* c, const float* d_imgs, int batch, int rows, int cols,
   return run_graphed(c, key, ptrs, body);
 }
 
+// The ranking scratch as sift_compute_batch carves it: the two row lists of
+// kp_cap ints, then their two counts.
+constexpr int kMaxComputeRows = 1 << 30;
+int compute_perm_ints(int kp_cap) { return 2 * kp_cap + 2; }
+
+// The device sequence of sift_compute_batch (Feature2D::compute for a batch):
+// pyramid -> gradient planes of scales 0..max_layer -> row prep -> the two
+// descriptor launches -> status block.  No detection, no host value; replayed
+// from the graph cache under sequence id 2.  With max_layer <= 3 the octaves
+// on the scatter blur leave plane 4 out (exact mode; the other blur forms
+// compute their scales together).
+int enqueue_compute(sift_ctx* c, const float* d_imgs, int batch, int rows, int cols, size_t row_stride,
+                    size_t img_stride, const sift_keypoint* d_kpts, const int* d_kp_offsets, int kp_cap, int max_layer,
+                    float* d_desc) {
+  const Layout L = make_layout(rows, cols, c->n_oct);
+  const Plane src{d_imgs, (long long)row_stride, (long long)img_stride};
+  if (int rc = check_fast(c, L, (long long)row_stride)) return rc;
+  if (int rc = ensure_perm(c, compute_perm_ints(kp_cap))) return rc;
+  unsigned skip4 = 0;
+  if (max_layer < kScales - 1 && !(c->flags & SIFT_FLAG_FAST))
+    for (int o = 0; o < L.n_oct; ++o)
+      if (use_sym_blur(c, L.oct[o].rows, L.oct[o].cols, batch)) skip4 |= 1u << o;
+  const DescLists lists{c->d_perm, c->d_perm + kp_cap, c->d_perm + 2 * (size_t)kp_cap};
+  auto body = [&]() {
+    enqueue_pyramid(c, L, src, batch, false, skip4);
+    {
+      StageScope s(c, ST_GRAD, 0, 12.0 * (max_layer + 1) * (double)L.g_img / kScales * batch);
+      launch_grad(c->stream, L, c->d_gpyr, c->d_grad, batch, 0, max_layer, c->d_mc);
+    }
+    {
+      StageScope s(c, ST_COMPUTE_PREP, 0, 36.0 * kp_cap);
+      launch_compute_prep(c->stream, L, d_kpts, d_kp_offsets, batch, kp_cap, max_layer, d_desc, c->d_err, lists);
+    }
+    {
+      StageScope s(c, ST_DESC);
+      launch_descriptors_listed(c->stream, L, c->d_grad, c->d_mc, d_kpts, d_kp_offsets, batch, kp_cap, d_desc,
+                                c->d_err, lists);
+    }
+    enqueue_status(c, false, nullptr, batch, kp_cap);  // no detection ran: assertion (and stall) bits only
+  };
+  std::vector<char> key, ptrs;
+  key_put(key, 2, batch, rows, cols, row_stride, img_stride, kp_cap, c->n_oct, c->flags, c->stall_once, max_layer);
+  key_put(ptrs, d_imgs, d_kpts, d_kp_offsets, d_desc);
+  return run_graphed(c, key, ptrs, body);
+}
+
 // Tail of the host detection calls.  upload() stages the input once; enqueue()
 // queues the device sequence, which ends in the status block.  ONE stream
 // synchronisation brings the keypoint count with it, then exactly n results
@@ -459,6 +505,54 @@ int sift_detect_compute_masked(sift_ctx* c, const float* img, int rows, int cols
 int sift_detect_compute(sift_ctx* c, const float* img, int rows, int cols, size_t row_stride_bytes,
                         sift_keypoint* kpts, float* desc, int cap, int* n_out) {
   return sift_detect_compute_masked(c, img, rows, cols, row_stride_bytes, nullptr, 0, kpts, desc, cap, n_out);
+}
+
+int sift_compute_batch(sift_ctx* c, const float* d_imgs, int batch, int rows, int cols, size_t row_stride,
+                       size_t img_stride, const sift_keypoint* d_kpts, const int* d_kp_offsets, int kp_cap,
+                       int max_layer, float* d_desc) {
+  if (!c) return SIFT_E_INVALID;
+  if (max_layer < 0 || max_layer > kScales - 1) return fail(c, SIFT_E_INVALID, "max_layer must be 0 .. 4");
+  if (batch < 0 || kp_cap < 0) return fail(c, SIFT_E_INVALID, "negative batch or kp_cap");
+  if (batch == 0 || kp_cap == 0) return SIFT_OK;  // no row to describe
+  if (!d_imgs || !d_kpts || !d_kp_offsets || !d_desc || row_stride < (size_t)(cols > 0 ? cols : 0))
+    return fail(c, SIFT_E_INVALID, "null buffer or bad stride");
+  if (int rc = check_dims(c, rows, cols, c->n_oct, batch)) return rc;
+  if (kp_cap > kMaxComputeRows) return fail(c, SIFT_E_SIZE, "kp_cap above 2^30 rows");
+  (void)hipSetDevice(c->device);
+  c->last_n = -1;
+  return enqueue_compute(c, d_imgs, batch, rows, cols, row_stride, img_stride, d_kpts, d_kp_offsets, kp_cap, max_layer,
+                         d_desc);
+}
+
+// Feature2D::compute from host memory: upload -> the graphed device sequence
+// with batch 1 on the context's own keypoint and descriptor buffers -> one
+// synchronisation -> n rows back.  The capacity named to the sequence is the
+// internal buffer's, so calls with other counts replay one captured sequence.
+int sift_compute(sift_ctx* c, const float* img, int rows, int cols, size_t row_stride_bytes, const sift_keypoint* kpts,
+                 int n, int max_layer, float* desc) {
+  if (!c) return SIFT_E_INVALID;
+  if (max_layer < 0 || max_layer > kScales - 1) return fail(c, SIFT_E_INVALID, "max_layer must be 0 .. 4");
+  if (n < 0) return fail(c, SIFT_E_INVALID, "negative keypoint count");
+  if (n == 0) return SIFT_OK;
+  if (!img || !kpts || !desc) return fail(c, SIFT_E_INVALID, "null buffer");
+  if (row_stride_bytes == 0) row_stride_bytes = (size_t)(cols > 0 ? cols : 0) * sizeof(float);
+  if (int rc = check_dims(c, rows, cols, c->n_oct, 1)) return rc;
+  if (n > kMaxComputeRows) return fail(c, SIFT_E_SIZE, "more than 2^30 keypoints");
+  (void)hipSetDevice(c->device);
+  if (int rc = ensure_kp(c, n)) return rc;
+  c->last_n = -1;  // the internal keypoint buffer is reused below
+  if (int rc = upload_image(c, img, rows, cols, row_stride_bytes)) return rc;
+  const int off[2] = {0, n};
+  HIP_TRY(c, hipMemcpyAsync(c->d_img_off, off, sizeof(off), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_kpts, kpts, sizeof(sift_keypoint) * n, hipMemcpyHostToDevice, c->stream));
+  if (int rc = enqueue_compute(c, c->d_in, 1, rows, cols, c->in_pitch, c->in_img, c->d_kpts, c->d_img_off,
+                               std::min(c->kp_cap, kMaxComputeRows), max_layer, c->d_desc))
+    return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // the rows are copied whatever the status says: an invalid row holds zeros
+  const int rc = take_status(c, false, kErrAssert | kErrStall);
+  HIP_TRY(c, hipMemcpy(desc, c->d_desc, sizeof(float) * kDescLen * n, hipMemcpyDeviceToHost));
+  return rc;
 }
 
 int sift_gaussian_blur(sift_ctx* c, const float* src, int rows, int cols, double sigma, float* dst) {

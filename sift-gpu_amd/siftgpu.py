@@ -100,6 +100,8 @@ def lib():
             "sift_detect_compute_batch": (ip, [vp, vp, ip, ip, ip, sz, sz, vp, vp, ip, vp]),
             "sift_detect_compute_masked": (ip, [vp, fp, ip, ip, sz, vp, sz, vp, fp, ip, pint]),
             "sift_detect_compute_batch_masked": (ip, [vp, vp, ip, ip, ip, sz, sz, vp, sz, sz, vp, vp, ip, vp]),
+            "sift_compute_batch": (ip, [vp, vp, ip, ip, ip, sz, sz, vp, vp, ip, ip, vp]),
+            "sift_compute": (ip, [vp, fp, ip, ip, sz, vp, ip, ip, fp]),
             "sift_copy_results": (ip, [vp, vp, fp, ip, pint]),
             "sift_synth_images": (ip, [vp, vp, ip, ip, ip, sz, sz, ip]),
             "sift_gaussian_blur": (ip, [vp, fp, ip, ip, ctypes.c_double, fp]),
@@ -166,7 +168,7 @@ def lib():
         }
         optional = {"sift_graph_stats", "sift_g4_fill_stats", "sift_set_max_features",
                     "sift_multi_set_max_features", "sift_detect_compute_masked", "sift_detect_compute_batch_masked",
-                    "sift_multi_step_masked"}  # absent from older builds (A/B runs against a saved library)
+                    "sift_multi_step_masked", "sift_compute_batch", "sift_compute"}  # absent from older builds (A/B runs against a saved library)
         for name, (res, args) in sigs.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -298,14 +300,20 @@ class Context:
         self._check("sift_set_max_features", self._L.sift_set_max_features(self.h, n))
 
     # ---- host-memory API (reference names) ------------------------------
-    def SIFT_NCL(self, img: np.ndarray, row_stride_bytes: int | None = None, mask=None):
-        """row_stride_bytes None: img is copied to a contiguous float32 array.
+    def SIFT_NCL(self, img: np.ndarray, row_stride_bytes: int | None = None, mask=None, keypoints=None):
+        """keypoints given (detectAndCompute's useProvidedKeypoints): they are described
+        unchanged -- (keypoints, self.compute(img, keypoints)) -- and the mask is
+        ignored, as OpenCV ignores it.  Otherwise:
+        row_stride_bytes None: img is copied to a contiguous float32 array.
         A number: img's own memory is passed with that row stride (img must be
         2-D float32 with unit column stride and rows that many bytes apart;
         0 is the ABI's default, cols * 4).
         mask: detectAndCompute's mask, a uint8 or bool array of the image's shape;
         a keypoint at (x, y) is dropped iff mask[int(y + 0.5), int(x + 0.5)] == 0
         (on the device, before the descriptors; include/sift_hip.h)."""
+        if keypoints is not None:
+            kps = np.ascontiguousarray(keypoints, KEYPOINT_DTYPE)
+            return kps, self.compute(img, kps)
         mask = _detection_mask(mask, np.shape(img))
         if row_stride_bytes is None:
             img = np.ascontiguousarray(img, np.float32)
@@ -374,6 +382,20 @@ class Context:
             rc = self._L.sift_copy_results(self.h, kps.ctypes.data, None, n.value, ctypes.byref(n))
             self._check("sift_copy_results", rc)
         return kps
+
+    def compute(self, img: np.ndarray, keypoints: np.ndarray, max_layer: int = 4) -> np.ndarray:
+        """Feature2D::compute: the descriptors [n, 128] of img at the given keypoints
+        (KEYPOINT_DTYPE rows, unchanged), in the pyramid SIFT_NCL builds for img.
+        max_layer: no keypoint names a scale above it (3 for detected keypoints
+        spares the widest blur).  A row outside the pyramid raises SiftError."""
+        img = np.ascontiguousarray(img, np.float32)
+        kps = np.ascontiguousarray(keypoints, KEYPOINT_DTYPE).reshape(-1)
+        r, c = img.shape
+        desc = np.zeros((len(kps), DESC_LEN), np.float32)
+        self._check("sift_compute",
+                    self._L.sift_compute(self.h, _fp(img), r, c, c * 4, kps.ctypes.data, len(kps), max_layer,
+                                         _fp(desc)))
+        return desc
 
     def calDescriptor(self, gpyr, keypoints: np.ndarray, firstOctave: int = 0) -> np.ndarray:
         r, c = gpyr[0].shape
@@ -790,6 +812,18 @@ class Context:
                                                              ctypes.c_void_p(kpts_ptr), ctypes.c_void_p(desc_ptr),
                                                              kp_cap, ctypes.c_void_p(offs_ptr)))
 
+    def compute_batch(self, imgs_ptr: int, batch: int, rows: int, cols: int, row_stride: int, img_stride: int,
+                      kpts_ptr: int, kp_offsets_ptr: int, kp_cap: int, desc_ptr: int, max_layer: int = 4):
+        """Device-pointer form (no sync) of Feature2D::compute for a batch: describes rows
+        [kp_offsets[b], kp_offsets[b+1]) of kpts_ptr in image b -- the offsets are device
+        ints as detect_compute_batch leaves them, clamped to kp_cap -- into the same rows of
+        desc_ptr.  max_layer: no row names a scale above it (include/sift_hip.h)."""
+        self._check("sift_compute_batch",
+                    self._L.sift_compute_batch(self.h, ctypes.c_void_p(imgs_ptr), batch, rows, cols, row_stride,
+                                               img_stride, ctypes.c_void_p(kpts_ptr),
+                                               ctypes.c_void_p(kp_offsets_ptr), kp_cap, max_layer,
+                                               ctypes.c_void_p(desc_ptr)))
+
     def selftest_math(self, op: int, a: np.ndarray, b: np.ndarray | None = None) -> np.ndarray:
         """One device helper element-wise (sift_hip.h lists ops 0..7); ops 8 / 9 are the
         homography's update_num_iters(0.995 / 0.5, (b - a) / b, 4, 2000) for a = good
@@ -974,10 +1008,18 @@ def _ctx(rows, cols):
     return _default
 
 
-def SIFT_NCL(image, mask=None):
-    """mask: detectAndCompute's mask (uint8 or bool, the image's shape; zero = no keypoint here)."""
+def SIFT_NCL(image, mask=None, keypoints=None):
+    """mask: detectAndCompute's mask (uint8 or bool, the image's shape; zero = no keypoint here).
+    keypoints: useProvidedKeypoints -- describe these and detect nothing; the mask is ignored."""
+    if keypoints is not None:
+        return _ctx(*image.shape).SIFT_NCL(image, keypoints=keypoints)
     mask = _detection_mask(mask, np.shape(image))
     return _ctx(*image.shape).SIFT_NCL(image, mask=mask)
+
+
+def compute(image, keypoints):
+    """Feature2D::compute(image, keypoints): the [n, 128] descriptors at the given keypoints."""
+    return _ctx(*np.shape(image)).compute(image, keypoints)
 
 
 def Gaussian_Blur(src, sigma):

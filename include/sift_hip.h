@@ -633,6 +633,60 @@ int sift_cross_match_segmented_device(sift_ctx* ctx, int metric, const void* d_q
                                       const sift_keypoint* d_t_kpts, sift_match* d_matches, float* d_src_xy,
                                       float* d_dst_xy, int m_cap, int* d_m_offsets);
 
+/* ---- matching within a search window (match_window.hip) --------------------- */
+/* The segmented matcher of the given SIFT_METRIC_* (rows of the metric's type,
+ * [q_cap][128] / [t_cap][128], 16-byte aligned) with one change: a train row is
+ * a candidate for a query row only if it is admissible -- what OpenCV spells as
+ * the mask argument of knnMatch, computed here from keypoint positions.
+ * Everything else is the dense segmented matcher's contract word for word:
+ * segments from device offsets with every bound clamped to q_cap / t_cap,
+ * d_t_offsets == NULL for a shared train set, indices local to the train range,
+ * k of 1 or 2, ascending (distance, local train index) with the lower index
+ * first at equal distance, idx -1 / dist +inf where fewer than k admissible rows
+ * at a finite distance exist, rows outside [clamp(q_offsets[0]),
+ * clamp(q_offsets[n_segments])) untouched, n_segments == 0 or q_cap == 0 SIFT_OK
+ * with nothing enqueued, enqueued on the context stream with no synchronisation
+ * and no host read of an offset.  Distances are the dense matchers' own bit for
+ * bit (float L1 in match.hip's summation order, the byte metrics exact
+ * integers), so d_idx / d_dist [q_cap][k] go to sift_ratio_matches_device and
+ * everything after it unchanged, and with radius = +inf, d_H = NULL and finite
+ * coordinates the output equals the dense call of the same metric byte for byte.
+ * Admissibility of train row t for query row q of segment b: the predicted
+ * position (px, py) is d_q_kpts[q]'s (x, y) itself when d_H == NULL or when
+ * d_found != NULL and d_found[b] == 0; otherwise it is sift_perspective_transform's
+ * value of H = d_H + 9 b at that point, |w| <= FLT_EPSILON -> (0, 0) included.
+ * d_H is [n_segments][9] doubles and d_found [n_segments] ints, exactly what
+ * sift_find_homography_segmented_device writes (src = query, dst = train), so
+ * pair b's model can gate pair b's next match with no host value.  t is
+ * admissible iff fabsf(tx - px) <= radius && fabsf(ty - py) <= radius, in float,
+ * (tx, ty) = d_t_kpts[t]'s (x, y) (d_t_kpts is indexed like d_train: row
+ * t_offsets[b] + local index): a closed square window; a NaN anywhere makes the
+ * row inadmissible; radius = +inf admits every row with comparable coordinates,
+ * radius = 0 only exactly coincident points.
+ * rows, cols: the train images' extent, a hint that shapes the search grid.  No
+ * result depends on it: coordinates outside [0, cols) x [0, rows), negatives
+ * and infinities included, are legal and get the rule's answer.
+ * The clamped train offsets must not decrease (ranges that overlap are searched
+ * memory-safely, but which of their rows are candidates is unspecified).
+ * SIFT_E_INVALID: NULL context, NULL required buffer (both keypoint arrays are
+ * required), unknown metric, k outside {1, 2}, radius negative or NaN, rows or
+ * cols < 1, unaligned rows.
+ * Out of scope: a gated reverse pass or a gated cross-check (they would need
+ * the inverse prior); no existing entry point changes. */
+int sift_knn_match_window_segmented_device(sift_ctx* ctx, int metric, const void* d_query,
+                                           const sift_keypoint* d_q_kpts, const int* d_q_offsets, int n_segments,
+                                           int q_cap, const void* d_train, const sift_keypoint* d_t_kpts,
+                                           const int* d_t_offsets /* NULL = shared */, int t_cap,
+                                           const double* d_H /* may be NULL */, const int* d_found /* may be NULL */,
+                                           float radius, int rows, int cols, int k, int* d_idx, float* d_dist);
+/* Host buffers (synchronous); query and q_kpts have q_cap rows, train and
+ * t_kpts t_cap rows, H n_segments x 9 doubles, found n_segments ints: */
+int sift_knn_match_window_segmented(sift_ctx* ctx, int metric, const void* query, const sift_keypoint* q_kpts,
+                                    const int* q_offsets, int n_segments, int q_cap, const void* train,
+                                    const sift_keypoint* t_kpts, const int* t_offsets /* NULL = shared */, int t_cap,
+                                    const double* H /* may be NULL */, const int* found /* may be NULL */,
+                                    float radius, int rows, int cols, int k, int* idx, float* dist);
+
 /* ---- homography ---------------------------------------- */
 /* Replaces `findHomography(obj, scene, RANSAC)` and `perspectiveTransform`
  * (src/main.cpp:54-62): n point pairs as interleaved (x, y) floats, OpenCV's

@@ -168,6 +168,48 @@ int knn_seg_l2_u8_device(sift_ctx* c, const uint8_t* q, const int* qoff, int n_s
   return SIFT_OK;
 }
 
+// ---- spatially gated matching: the segmented matcher of a metric inside a search window (match_window.hip) ----
+bool known_metric(int metric) {
+  return metric == SIFT_METRIC_L1_F32 || metric == SIFT_METRIC_L1_U8 || metric == SIFT_METRIC_L2SQR_U8;
+}
+const char* const kBadMetric = "metric must be one of SIFT_METRIC_L1_F32, _L1_U8, _L2SQR_U8";
+size_t metric_row_bytes(int metric) { return metric == SIFT_METRIC_L1_F32 ? kDescLen * sizeof(float) : kDescLen; }
+
+int check_window(sift_ctx* c, int metric, const void* query, const sift_keypoint* q_kpts, const int* q_offsets,
+                 int n_segments, int q_cap, const void* train, const sift_keypoint* t_kpts, int t_cap, float radius,
+                 int rows, int cols, int k, const int* idx, const float* dist) {
+  if (!c) return SIFT_E_INVALID;
+  if (!known_metric(metric)) return fail(c, SIFT_E_INVALID, kBadMetric);
+  if (n_segments < 0 || q_cap < 0 || t_cap < 0) return fail(c, SIFT_E_INVALID, "negative count");
+  if (k != 1 && k != 2) return fail(c, SIFT_E_INVALID, "k must be 1 or 2");
+  if (!(radius >= 0)) return fail(c, SIFT_E_INVALID, "radius must be 0 or positive (+inf: no gate)");
+  if (rows < 1 || cols < 1) return fail(c, SIFT_E_INVALID, "rows and cols must be at least 1");
+  if (n_segments == 0 || q_cap == 0) return SIFT_OK;
+  if (!query || !q_offsets || !idx || !dist || (t_cap > 0 && !train)) return fail(c, SIFT_E_INVALID, "null buffer");
+  if (!q_kpts || !t_kpts) return fail(c, SIFT_E_INVALID, "the window needs both keypoint arrays");
+  return SIFT_OK;
+}
+
+// A: everything but the grid and the scratch pieces.
+int window_device(sift_ctx* c, WindowArgs A, WindowGrid G, WindowParts P) {
+  A.nx = G.nx;
+  A.ny = G.ny;
+  A.inv_cell = G.inv_cell;
+  A.cell_end = P.cell_end;
+  A.cell_rows = P.cell_rows;
+  A.cell_xy = dev(P.cell_xy);
+  {
+    StageScope sc(c, ST_WINDOW_BIN, 0, 2.0 * (sizeof(sift_keypoint) + 12.0) * A.t_cap);
+    HIP_TRY(c, launch_window_bin(c->stream, A));
+  }
+  {
+    StageScope sc(c, ST_MATCH_WINDOW);  // the work depends on offsets and positions only the device knows
+    launch_knn_window(c->stream, A);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
 // ---- cross-check: the join of a forward and a reverse matcher result (cross_check.hip) ----
 // The checks of the train offsets and the outputs, and of the ratio: shared with the one-call form.
 int check_cross_out(sift_ctx* c, const int* t_offsets, const sift_keypoint* q_kpts, const sift_keypoint* t_kpts,
@@ -705,6 +747,102 @@ int sift_cross_match_segmented_device(sift_ctx* c, int metric, const void* d_que
   }
   return cross_device(c, T.idx, T.dist, fwd_k, d_q_offsets, n_segments, q_cap, T.ridx, 1, d_t_offsets, t_cap, ratio,
                       d_q_kpts, d_t_kpts, d_matches, d_src_xy, d_dst_xy, m_cap, d_m_offsets, T.blk_scan);
+}
+
+int sift_knn_match_window_segmented_device(sift_ctx* c, int metric, const void* d_query,
+                                           const sift_keypoint* d_q_kpts, const int* d_q_offsets, int n_segments,
+                                           int q_cap, const void* d_train, const sift_keypoint* d_t_kpts,
+                                           const int* d_t_offsets, int t_cap, const double* d_H, const int* d_found,
+                                           float radius, int rows, int cols, int k, int* d_idx, float* d_dist) {
+  int rc = check_window(c, metric, d_query, d_q_kpts, d_q_offsets, n_segments, q_cap, d_train, d_t_kpts, t_cap,
+                        radius, rows, cols, k, d_idx, d_dist);
+  if (rc || n_segments == 0 || q_cap == 0) return rc;
+  if (!aligned16(d_query, d_train)) return fail(c, SIFT_E_INVALID, kRowsUnaligned);
+  (void)hipSetDevice(c->device);
+  const int n_grids = d_t_offsets ? n_segments : 1;
+  const WindowGrid G = window_grid(radius, rows, cols, t_cap, n_grids);
+  WindowParts P;
+  if ((rc = carve(c, &P, [&](Carver& a) { return window_layout(a, n_grids, G.nx * G.ny, t_cap); }))) return rc;
+  WindowArgs A{};
+  A.metric = metric;
+  A.q = d_query;
+  A.q_kpts = d_q_kpts;
+  A.qoff = d_q_offsets;
+  A.nseg = n_segments;
+  A.q_cap = q_cap;
+  A.t = d_train;
+  A.t_kpts = d_t_kpts;
+  A.toff = d_t_offsets;
+  A.t_cap = t_cap;
+  A.H = d_H;
+  A.found = d_found;
+  A.radius = radius;
+  A.k = k;
+  A.idx = d_idx;
+  A.dist = d_dist;
+  return window_device(c, A, G, P);
+}
+
+int sift_knn_match_window_segmented(sift_ctx* c, int metric, const void* query, const sift_keypoint* q_kpts,
+                                    const int* q_offsets, int n_segments, int q_cap, const void* train,
+                                    const sift_keypoint* t_kpts, const int* t_offsets, int t_cap, const double* H,
+                                    const int* found, float radius, int rows, int cols, int k, int* idx,
+                                    float* dist) {
+  int rc = check_window(c, metric, query, q_kpts, q_offsets, n_segments, q_cap, train, t_kpts, t_cap, radius, rows,
+                        cols, k, idx, dist);
+  if (rc || n_segments == 0 || q_cap == 0) return rc;
+  (void)hipSetDevice(c->device);
+  const int n_grids = t_offsets ? n_segments : 1;
+  const WindowGrid G = window_grid(radius, rows, cols, t_cap, n_grids);
+  const size_t row = metric_row_bytes(metric);
+  WindowHost S;
+  if ((rc = carve(c, &S, [&](Carver& a) {
+         return window_host_layout(a, n_segments, q_cap, t_cap, row, t_offsets != nullptr, H != nullptr,
+                                   found != nullptr, k, n_grids, G.nx * G.ny);
+       })))
+    return rc;
+  const size_t ob = (size_t)(n_segments + 1) * sizeof(int);
+  HIP_TRY(c, hipMemcpyAsync(S.query, query, q_cap * row, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.q_kpts, q_kpts, (size_t)q_cap * sizeof(sift_keypoint), hipMemcpyHostToDevice,
+                            c->stream));
+  if (t_cap) {
+    HIP_TRY(c, hipMemcpyAsync(S.train, train, t_cap * row, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(S.t_kpts, t_kpts, (size_t)t_cap * sizeof(sift_keypoint), hipMemcpyHostToDevice,
+                              c->stream));
+  }
+  HIP_TRY(c, hipMemcpyAsync(S.q_off, q_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  if (S.t_off) HIP_TRY(c, hipMemcpyAsync(S.t_off, t_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  if (S.H)
+    HIP_TRY(c, hipMemcpyAsync(S.H, H, (size_t)n_segments * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (S.found)
+    HIP_TRY(c, hipMemcpyAsync(S.found, found, (size_t)n_segments * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  WindowArgs A{};
+  A.metric = metric;
+  A.q = S.query;
+  A.q_kpts = S.q_kpts;
+  A.qoff = S.q_off;
+  A.nseg = n_segments;
+  A.q_cap = q_cap;
+  A.t = S.train;
+  A.t_kpts = S.t_kpts;
+  A.toff = S.t_off;
+  A.t_cap = t_cap;
+  A.H = S.H;
+  A.found = S.found;
+  A.radius = radius;
+  A.k = k;
+  A.idx = S.idx;
+  A.dist = S.dist;
+  if ((rc = window_device(c, A, G, S.win))) return rc;
+  // only the live rows come back: the others are left untouched, as in the device form
+  const int lo = clamp_off(q_offsets[0], q_cap), hi = clamp_off(q_offsets[n_segments], q_cap);
+  if (hi > lo) {
+    const size_t n = (size_t)(hi - lo) * k, o = (size_t)lo * k;
+    HIP_TRY(c, hipMemcpyAsync(idx + o, S.idx + o, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dist + o, S.dist + o, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SIFT_OK;
 }
 
 int sift_bgr8_to_gray_device(sift_ctx* c, const uint8_t* d_bgr, int batch, int rows, int cols, size_t row_stride,

@@ -1,6 +1,8 @@
 // block_scan.hpp -- the one-workgroup scan of per-block counts that the ordered
 // compactions share (match.hip: the ratio stage; cross_check.hip: the
-// cross-check stage).  Device code, included by those two files only.
+// cross-check stage), and of the per-cell counts of the windowed matcher's grids
+// (match_window.hip, one workgroup per grid).  Device code, included by those
+// three files only.
 #pragma once
 
 #include "common.hpp"
@@ -9,8 +11,10 @@ namespace sift {
 
 namespace {
 
-// in-place exclusive scan of v[0..n), v[n] = total (one workgroup)
+// in-place exclusive scan of v[0..n), v[n] = total (one workgroup); workgroup g
+// of a larger grid scans the g-th array of n + 1 entries
 __global__ __launch_bounds__(1024) void ratio_scan_kernel(int* __restrict__ v, int n) {
+  v += (long long)blockIdx.x * (n + 1);
   __shared__ int wsum[16];
   __shared__ int carry_s;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;

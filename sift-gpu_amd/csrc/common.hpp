@@ -331,6 +331,40 @@ void launch_cross_check(hipStream_t st, const int* idx, const float* dist, int f
                         int q_cap, const int* ridx, int rev_k, const int* toff, int t_cap, double ratio,
                         const sift_keypoint* q_kpts, const sift_keypoint* t_kpts, sift_match* matches, float* src_xy,
                         float* dst_xy, int m_cap, int* moff, int* blk_scan);
+// match_window.hip: the spatially gated segmented matcher.  launch_window_bin
+// sorts the train keypoints of every grid (one per train segment, one in all
+// for a shared train set) into the cells of an nx x ny grid of side
+// 1 / inv_cell: cell_end is [n_grids][nx * ny + 1] ints (after the launch,
+// entry c is the end of cell c's run, entry c - 1 its start), cell_rows /
+// cell_xy [max(t_cap, 1)] the local train indices and positions in cell order,
+// each grid's run starting at its train range's first row.
+// launch_knn_window then scores, per query, the admissible rows of the cells
+// its window touches.  The grid's shape is scratch.hpp's window_grid(); no
+// result depends on it.
+struct WindowArgs {
+  int metric;  // SIFT_METRIC_*
+  const void* q;
+  const sift_keypoint* q_kpts;
+  const int* qoff;
+  int nseg, q_cap;
+  const void* t;
+  const sift_keypoint* t_kpts;
+  const int* toff;  // nullptr: shared train
+  int t_cap;
+  const double* H;   // nullptr: the query position itself
+  const int* found;  // nullptr: every H is used
+  float radius;
+  int nx, ny;
+  float inv_cell;
+  int* cell_end;
+  int* cell_rows;
+  float2* cell_xy;
+  int k;
+  int* idx;
+  float* dist;
+};
+hipError_t launch_window_bin(hipStream_t st, const WindowArgs& A);
+void launch_knn_window(hipStream_t st, const WindowArgs& A);
 // pyramid_pc.hip (SIFT_FLAG_FAST): octave o's five planes by the separable
 // form, plus octave o+1's plane 0 when pyramid_fuses_decimation(L, o + 1)
 // (else decimate first), from a producer wave and three consumer waves

@@ -1,11 +1,13 @@
-// scratch.hpp -- how the matcher, byte-matcher, cross-check, front-end and segmented-homography entry
+// scratch.hpp -- how the matcher, byte-matcher, windowed-matcher, cross-check, front-end and segmented-homography entry
 // points divide the context's one scratch block (sift_ctx::d_match).  Each
 // layout is described once, as a function of a Carver, and run twice: on a null
 // base to measure the block, then on the block itself.  Plain host C++ (no HIP
 // include), so that tests/cpp/scratch_layout.cpp, match_u8_layout.cpp,
-// match_l2_u8_layout.cpp, cross_check_layout.cpp and homography_layout.cpp check every layout without a GPU.
+// match_l2_u8_layout.cpp, cross_check_layout.cpp, homography_layout.cpp and match_window_layout.cpp check every
+// layout without a GPU.
 #pragma once
 
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -213,6 +215,56 @@ inline CrossMatch<SegPartsL2U8> cross_match_l2_u8_layout(Carver& a, int n_segmen
                                                          int fwd_splits, int rev_splits, int blocks) {
   return {cross_tables(a, q_cap, fwd_k, t_cap, blocks), seg_l2_u8_layout(a, n_segments, q_cap, t_cap, fwd_splits),
           seg_l2_u8_layout(a, n_segments, t_cap, q_cap, rev_splits)};
+}
+
+// ---- spatially gated matching (match_window.hip) ----
+// The search grid of sift_knn_match_window_segmented_device, from host
+// arguments only: square cells of side max(radius, 1 px), grown until one grid
+// has at most window_cell_cap() cells -- kWindowMaxCells, and no more than four
+// per train row of an even share of the buffer (finer cells than that hold
+// nothing).  radius = +inf is one cell.  The extent rows x cols is a hint: the
+// kernels clamp every point to the border cells, and no result depends on the
+// grid's shape.
+constexpr int kWindowMaxCells = 4096;
+struct WindowGrid { int nx, ny; float inv_cell; };
+inline int window_cell_cap(int t_cap, int n_grids) {
+  const long long per = ((long long)t_cap + n_grids - 1) / n_grids * 4;
+  return per < 1 ? 1 : (per > kWindowMaxCells ? kWindowMaxCells : (int)per);
+}
+inline WindowGrid window_grid(float radius, int rows, int cols, int t_cap, int n_grids) {
+  const double cap = window_cell_cap(t_cap, n_grids);
+  double cell = radius > 1.f ? (double)radius : 1.;
+  if (cell > 2e9) return {1, 1, 0.f};  // wider than any extent, +inf included
+  for (;; cell *= 1.125) {
+    const double nx = ceil(cols / cell), ny = ceil(rows / cell);
+    if (nx * ny <= cap) return {(int)nx, (int)ny, (float)(1. / cell)};
+  }
+}
+
+// sift_knn_match_window_segmented_device: per grid (one per train segment, one
+// in all for a shared train set) the scanned cell counts and their total, then
+// the local train indices and the positions in cell order, one per train row.
+struct WindowParts { int* cell_end; int* cell_rows; Float2* cell_xy; };
+inline WindowParts window_layout(Carver& a, int n_grids, int n_cells, int t_cap) {
+  return {a.take<int>((size_t)n_grids * ((size_t)n_cells + 1)), a.take<int>(at_least_one(t_cap)),
+          a.take<Float2>(at_least_one(t_cap))};
+}
+
+// sift_knn_match_window_segmented: the staged rows (row_bytes each: 512 for
+// float rows, 128 for byte rows), keypoints, results and offsets -- t_off, H
+// and found keep their places when the caller has none, and are null then --
+// then the device form's pieces.
+struct WindowHost {
+  uint8_t *query, *train; sift_keypoint *q_kpts, *t_kpts; int* idx; float* dist; int *q_off, *t_off; double* H;
+  int* found; WindowParts win;
+};
+inline WindowHost window_host_layout(Carver& a, int n_segments, int q_cap, int t_cap, size_t row_bytes, bool has_t_off,
+                                     bool has_H, bool has_found, int k, int n_grids, int n_cells) {
+  return {a.take<uint8_t>((size_t)q_cap * row_bytes), a.take<uint8_t>(at_least_one(t_cap) * row_bytes),
+          a.take<sift_keypoint>((size_t)q_cap), a.take<sift_keypoint>(at_least_one(t_cap)),
+          a.take<int>((size_t)q_cap * k), a.take<float>((size_t)q_cap * k), a.take<int>((size_t)n_segments + 1),
+          a.take_if<int>(has_t_off, (size_t)n_segments + 1), a.take_if<double>(has_H, (size_t)n_segments * 9),
+          a.take_if<int>(has_found, (size_t)n_segments), window_layout(a, n_grids, n_cells, t_cap)};
 }
 
 // sift_bgr8_to_gray: the strided source rows, then the packed gray image.

@@ -141,6 +141,10 @@ def lib():
                                               vp, vp, fp, fp, ip, pint]),
             "sift_cross_match_segmented_device": (ip, [vp, ip, vp, vp, ip, ip, vp, vp, ip, ctypes.c_double, vp, vp,
                                                        vp, vp, vp, ip, vp]),
+            "sift_knn_match_window_segmented_device": (ip, [vp, ip, vp, vp, vp, ip, ip, vp, vp, vp, ip, vp, vp,
+                                                            ctypes.c_float, ip, ip, ip, vp, vp]),
+            "sift_knn_match_window_segmented": (ip, [vp, ip, vp, vp, pint, ip, ip, vp, vp, pint, ip, vp, pint,
+                                                     ctypes.c_float, ip, ip, ip, pint, fp]),
             "sift_find_homography_segmented_device": (ip, [vp, vp, vp, vp, ip, ip, ctypes.c_double, ip,
                                                            ctypes.c_double, vp, vp, vp]),
             "sift_find_homography_segmented": (ip, [vp, fp, fp, pint, ip, ip, ctypes.c_double, ip, ctypes.c_double,
@@ -168,7 +172,8 @@ def lib():
         }
         optional = {"sift_graph_stats", "sift_g4_fill_stats", "sift_set_max_features",
                     "sift_multi_set_max_features", "sift_detect_compute_masked", "sift_detect_compute_batch_masked",
-                    "sift_multi_step_masked", "sift_compute_batch", "sift_compute"}  # absent from older builds (A/B runs against a saved library)
+                    "sift_multi_step_masked", "sift_compute_batch", "sift_compute",
+                    "sift_knn_match_window_segmented_device", "sift_knn_match_window_segmented"}  # absent from older builds (A/B runs against a saved library)
         for name, (res, args) in sigs.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -654,6 +659,65 @@ class Context:
                                                     idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _fp(dist)))
         return idx, dist
 
+    # ---- matching within a search window (spatially gated kNN) for a whole batch ----
+    def knn_match_window_segmented_device(self, metric: int, query_ptr: int, q_kpts_ptr: int, q_offsets_ptr: int,
+                                          n_segments: int, q_cap: int, train_ptr: int, t_kpts_ptr: int,
+                                          t_offsets_ptr: int | None, t_cap: int, H_ptr: int | None,
+                                          found_ptr: int | None, radius: float, rows: int, cols: int, k: int,
+                                          idx_ptr: int, dist_ptr: int):
+        """Device-pointer form (no sync) of the windowed matcher: the segmented
+        matcher of the metric (SIFT_METRIC_L1_F32 / _L1_U8 / _L2SQR_U8), where a
+        train row is a candidate only if its keypoint lies within `radius` (a closed
+        square, float compare) of the query keypoint's predicted position: the
+        position itself (H_ptr None, or found[b] == 0), else H[b] applied to it
+        (H [n_segments][9] float64 and found [n_segments] int32 as
+        find_homography_segmented_device writes them).  rows, cols: the train
+        images' extent, a hint for the search grid only.  Same outputs and contract
+        as knn_match_segmented_device otherwise."""
+        vp = lambda p: ctypes.c_void_p(p or None)  # noqa: E731
+        self._check("sift_knn_match_window_segmented_device",
+                    self._L.sift_knn_match_window_segmented_device(
+                        self.h, int(metric), vp(query_ptr), vp(q_kpts_ptr), vp(q_offsets_ptr), n_segments, q_cap,
+                        vp(train_ptr), vp(t_kpts_ptr), vp(t_offsets_ptr), t_cap, vp(H_ptr), vp(found_ptr),
+                        float(radius), rows, cols, k, vp(idx_ptr), vp(dist_ptr)))
+
+    def knnMatchWindowSegmented(self, metric: int, query: np.ndarray, q_kpts: np.ndarray, q_offsets,
+                                train: np.ndarray, t_kpts: np.ndarray, t_offsets=None, radius: float = 32.0,
+                                H=None, found=None, image_size=(1080, 1920), k: int = 2):
+        """knn_match_window_segmented_device on host arrays (synchronous): idx int32,
+        dist float32 [len(query), k].  query / train are float32 rows for
+        SIFT_METRIC_L1_F32 and uint8 rows otherwise; q_kpts / t_kpts are
+        KEYPOINT_DTYPE arrays, one per row; H is [n_segments, 9] (or [n_segments, 3,
+        3]) float64, found [n_segments] int32; image_size = (rows, cols)."""
+        if metric == SIFT_METRIC_L1_F32:
+            q = np.ascontiguousarray(query, np.float32).reshape(-1, DESC_LEN)
+            t = np.ascontiguousarray(train, np.float32).reshape(-1, DESC_LEN)
+        else:
+            q, t = self._u8_rows(query), self._u8_rows(train)
+        qk, tk = np.ascontiguousarray(q_kpts, KEYPOINT_DTYPE), np.ascontiguousarray(t_kpts, KEYPOINT_DTYPE)
+        if len(qk) != len(q) or len(tk) != len(t):
+            raise ValueError("one keypoint per descriptor row")
+        qo = np.ascontiguousarray(q_offsets, np.int32)
+        to = None if t_offsets is None else np.ascontiguousarray(t_offsets, np.int32)
+        if qo.ndim != 1 or len(qo) < 1 or (to is not None and to.shape != qo.shape):
+            raise ValueError("offsets must be 1-D, n_segments + 1 entries each")
+        n = len(qo) - 1
+        Hh = None if H is None else np.ascontiguousarray(H, np.float64).reshape(-1, 9)
+        fh = None if found is None else np.ascontiguousarray(found, np.int32)
+        if (Hh is not None and len(Hh) != n) or (fh is not None and fh.shape != (n,)):
+            raise ValueError("H is [n_segments, 9], found [n_segments]")
+        pint = ctypes.POINTER(ctypes.c_int)
+        idx = np.full((len(q), k), -1, np.int32)
+        dist = np.full((len(q), k), np.inf, np.float32)
+        self._check("sift_knn_match_window_segmented",
+                    self._L.sift_knn_match_window_segmented(
+                        self.h, int(metric), q.ctypes.data, qk.ctypes.data, qo.ctypes.data_as(pint), n, len(q),
+                        t.ctypes.data, tk.ctypes.data, None if to is None else to.ctypes.data_as(pint), len(t),
+                        None if Hh is None else Hh.ctypes.data, None if fh is None else fh.ctypes.data_as(pint),
+                        float(radius), int(image_size[0]), int(image_size[1]), k, idx.ctypes.data_as(pint),
+                        _fp(dist)))
+        return idx, dist
+
     # ---- cross-check (mutual nearest neighbours) for a whole batch ------------
     def cross_check_matches_device(self, idx_ptr: int, dist_ptr: int, fwd_k: int, q_offsets_ptr: int, n_segments: int,
                                    q_cap: int, ridx_ptr: int, rev_k: int, t_offsets_ptr: int, t_cap: int,
@@ -1085,8 +1149,11 @@ NORM_L2SQR = 5  # cv::NORM_L2SQR
 class BFMatcher:
     """`cv::BFMatcher(NORM_L1)` as the reference uses it (src/main.cpp:25-27):
     knnMatch(queryDescriptors, trainDescriptors, k) -> per query a list of up to
-    k DMatch, nearest first.  k in (1, 2), no masks / crossCheck (the reference
-    uses none).  NORM_L1: float descriptors take the float matcher; two uint8
+    k DMatch, nearest first.  k in (1, 2), no mask argument / crossCheck (the
+    reference uses none); the mask that matters in practice, a search window
+    around each keypoint's predicted position, is the module function
+    window_match(query_desc, query_kpts, train_desc, train_kpts, radius, H).
+    NORM_L1: float descriptors take the float matcher; two uint8
     arrays take the byte matcher (integer distances).  NORM_L2SQR: two uint8
     arrays only, DMatch.distance is the squared distance (for a ratio test use
     ratio_test(matches, ratio ** 2)).  NORM_L2 (the square root) is not
@@ -1135,6 +1202,36 @@ def cross_check_match(query, train, normType: int = NORM_L1, ctx: Context | None
     ridx, _ = knn(t, to, q, qo, 1)
     m, _, _, _ = ctx.crossCheckMatches(idx, ridx, qo, to, dist)
     return [DMatch(int(r["query"]), int(r["train"]), 0, float(r["distance"])) for r in m]
+
+
+def window_match(query_desc, query_kpts, train_desc, train_kpts, radius, H=None, normType: int = NORM_L1,
+                 k: int = 2, image_size=None, ctx: Context | None = None):
+    """`BFMatcher(normType).knnMatch(query, train, k, mask)` for one pair of
+    descriptor sets, with the mask of guided matching: train row t is a candidate
+    for query row q only if |tx - px| <= radius and |ty - py| <= radius (float32),
+    (px, py) being q's keypoint position, or H (3 x 3, query -> train) applied to
+    it.  Per query a list of up to k DMatch, nearest first.  The matcher is picked
+    from the dtypes as BFMatcher.knnMatch picks it.  image_size = (rows, cols) of
+    the train image only shapes the search grid (default: the extent of the train
+    keypoints); no result depends on it."""
+    both_u8 = np.asarray(query_desc).dtype == np.uint8 and np.asarray(train_desc).dtype == np.uint8
+    if normType not in (NORM_L1, NORM_L2SQR):
+        raise ValueError("only NORM_L1 and NORM_L2SQR are implemented")
+    if normType == NORM_L2SQR and not both_u8:
+        raise ValueError("NORM_L2SQR takes two uint8 descriptor arrays")
+    metric = SIFT_METRIC_L2SQR_U8 if normType == NORM_L2SQR else SIFT_METRIC_L1_U8 if both_u8 else SIFT_METRIC_L1_F32
+    q = np.asarray(query_desc).reshape(-1, DESC_LEN)
+    t = np.asarray(train_desc).reshape(-1, DESC_LEN)
+    tk = np.ascontiguousarray(train_kpts, KEYPOINT_DTYPE)
+    if image_size is None:
+        ext = [tk[f][np.isfinite(tk[f])] for f in ("y", "x")]
+        image_size = tuple(int(min(max(float(e.max()) + 1, 1), 1 << 30)) if len(e) else 1 for e in ext)
+    ctx = ctx or _ctx(1, 1)
+    idx, dist = ctx.knnMatchWindowSegmented(metric, q, query_kpts, [0, len(q)], t, tk, None, radius,
+                                            None if H is None else np.asarray(H, np.float64).reshape(1, 9), None,
+                                            image_size, k)
+    return [[DMatch(i, int(idx[i, j]), 0, float(dist[i, j])) for j in range(k) if idx[i, j] >= 0]
+            for i in range(len(idx))]
 
 
 def ratio_test(matches, ratio: float = 0.86):

@@ -86,9 +86,14 @@ void SIFT_NCL(InputArray image, InputArray mask, std::vector<KeyPoint>& keypoint
  * (Feature2D::compute) in the pyramid SIFT_NCL builds for the image, and the
  * mask is ignored, as OpenCV ignores it.  OpenCV upsamples the image when a
  * keypoint has a negative octave; the reference never does, so such a keypoint
- * (or one whose octave or layer is outside the pyramid) makes the call throw. */
+ * (or one whose octave or layer is outside the pyramid) makes the call throw --
+ * unless upsample is set.
+ * upsample: SIFT::create()'s default firstOctave = -1 (sift_set_upsample in
+ * sift_hip.h).  The image is doubled on the GPU and the same sequence runs on
+ * it; keypoints come out in the original image's frame with octave bytes from
+ * 255 (octave -1) up, and provided keypoints may name octave -1. */
 void SIFT_NCL(InputArray image, InputArray mask, std::vector<KeyPoint>& keypoints, OutputArray descriptors,
-              bool useProvidedKeypoints);
+              bool useProvidedKeypoints, bool upsample = false);
 
 /* Sub modules */
 void Gaussian_Blur(Mat& src, Mat& dst, double sigma);

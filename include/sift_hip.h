@@ -117,6 +117,42 @@ int sift_set_candidate_capacity(sift_ctx* ctx, int per_image);
  * (OpenCV filters in detectAndCompute, not there).  n_per_image < 0 or a NULL
  * context: SIFT_E_INVALID, the setting is unchanged. */
 int sift_set_max_features(sift_ctx* ctx, int n_per_image);
+/* The upsampled first octave: Lowe's "octave -1", SIFT::create()'s default
+ * firstOctave = -1, which the reference leaves out (its createInitialImage
+ * ignores doubleSize).  on == 0 (the default) launches nothing, allocates
+ * nothing and leaves every output as it is.  With on != 0, sift_detect_compute,
+ * sift_detect_compute_masked, sift_detect_compute_batch[_masked], sift_compute
+ * and sift_compute_batch double each image on the device into a buffer the
+ * context owns (sift_upsample2x_device's rule, below; the buffer is allocated by
+ * the first upsampled call) and run their sequence, unchanged, on the
+ * 2 rows x 2 cols image: the reference's base blur sqrt(1.6^2 + 0.2^2) -- not
+ * OpenCV's sqrt(sigma^2 - 1) for a doubled image, which is out of scope -- the
+ * context's octave count applied to the doubled image (a caller who wants the
+ * same coarsest octave sets one more), exact mode and SIFT_FLAG_FAST alike.
+ * The context must have been created for the doubled shape: 2 rows > max_rows
+ * or 2 cols > max_cols is SIFT_E_SIZE, and the candidate capacity and the
+ * SIFT_E_WORKSPACE rule are the doubled image's.
+ * Keypoints come out in the original image's frame, by OpenCV's post-pass in
+ * detectAndCompute for firstOctave < 0, applied where the keypoints are
+ * emitted: x, y and size are multiplied by 0.5f (exact), the low byte of
+ * octave is decremented -- (octave & ~255) | ((octave - 1) & 255), so 255 is
+ * octave -1 -- and angle, response and class_id are unchanged.  Each image's
+ * keypoints are the doubled run's, in its order; each descriptor row is the
+ * doubled run's bit for bit (the descriptor stage runs with first_octave = -1,
+ * and unpackOctave maps each emitted row back onto the doubled pyramid exactly).
+ * The keypoint budget selects as in the doubled run (responses are unchanged).
+ * A detection mask stays rows x cols of the original image and is read at the
+ * emitted coordinates, mask[(int)(y + 0.5f)][(int)(x + 0.5f)].
+ * sift_compute[_batch]: keypoints are in original-image coordinates, the
+ * pyramid is the doubled image's, first_octave is -1, and the valid octaves
+ * are -1 .. n_octaves - 2; with the setting off a row with octave -1 stays an
+ * invalid row.  The setting is part of the graph-cache key of both sequences.
+ * Not applied by sift_find_scale_space_extrema (OpenCV rescales in
+ * detectAndCompute, not there) nor by the other sub-module calls.  sift_multi_*
+ * has no such setting: multi.hip calls no library function beyond those it
+ * already did (tests/cpp/multi_sim.cpp links it against its own stand-ins).
+ * A NULL context: SIFT_E_INVALID. */
+int sift_set_upsample(sift_ctx* ctx, int on);
 const char* sift_version(void);
 /* hipGraph cache counters of this context: sequences captured, cached
  * executables patched in place (hipGraphExecUpdate: same shape, other
@@ -231,14 +267,18 @@ int sift_detect_compute_masked(sift_ctx* ctx, const float* img, int rows, int co
  * call wrote (under SIFT_FLAG_FAST too, on the fast pyramid).  Angles follow
  * sift_calc_descriptors' contract (the bin wraps modulo 8).
  * firstOctave: OpenCV derives it from the keypoints and upsamples the image for
- * a negative octave; the reference never upsamples, so here the pyramid starts
- * at octave 0 and a row with a negative octave is an invalid row.
+ * a negative octave; the reference never upsamples, so unless
+ * sift_set_upsample is on the pyramid starts at octave 0 and a row with a
+ * negative octave is an invalid row.  With sift_set_upsample on, the pyramid
+ * is the doubled image's, firstOctave is -1, the rows stay in original-image
+ * coordinates and the valid octaves are -1 .. n_octaves - 2 (see there).
  * max_layer, 0 .. 4 (else SIFT_E_INVALID), is the caller's promise that no row
  * names a scale above it: only scales 0 .. max_layer are differentiated, and
  * with max_layer <= 3 the widest blur (w = 18) is not computed where the blur
  * form in use can leave it out.  4 admits every scale the reference allows; 3
  * covers every keypoint a SIFT detection emits.
- * Invalid rows: octave < 0, octave >= the context's octave count, layer > 4 or
+ * Invalid rows: octave < 0, octave >= the context's octave count (with
+ * sift_set_upsample on: octave < -1, octave >= the count - 1), layer > 4 or
  * layer > max_layer.  Such a row gets 128 zeros and sets the sticky assertion
  * bit, which sift_sync reports as SIFT_E_INVALID once; other rows are not
  * affected.
@@ -399,6 +439,41 @@ int sift_bgr8_to_gray(sift_ctx* ctx, const uint8_t* bgr, int rows, int cols, siz
 int sift_bgr8_to_gray_device(sift_ctx* ctx, const uint8_t* d_bgr, int batch, int rows, int cols,
                              size_t row_stride, size_t img_stride, int out_rows, int out_cols, float* d_gray,
                              size_t out_row_stride, size_t out_img_stride);
+
+/* ---- the doubled image (sift_set_upsample's first step, usable on its own) --
+ * dst = cv::resize(src, Size(2 * cols, 2 * rows), 0, 0, INTER_LINEAR) on
+ * CV_32F, stated here as the library's own rule (restated in numpy in
+ * tests/upsample_inputs.py); parity against OpenCV itself is by construction
+ * and unpinned, as for the homography (no OpenCV here).  A horizontal pass,
+ * then a vertical pass, both in float, every value formed as a * w0 + b * w1
+ * with two multiplies and one add, never fused.  For destination index d along
+ * an axis of n source samples S (columns and rows alike):
+ *     d even: s = d / 2 - 1,   weights (0.25f, 0.75f) on (S[s], S[s + 1])
+ *     d odd:  s = (d - 1) / 2, weights (0.75f, 0.25f)
+ *     s < 0:      the value is S[0], copied (no multiply)
+ *     s >= n - 1: the value is S[n - 1], copied (no multiply)
+ *     D[dy][dx] = Hrow[j0][dx] * v0 + Hrow[j1][dx] * v1,
+ *     Hrow[r][dx] = S[r][i0] * w0 + S[r][i1] * w1.
+ * A 1 x 1 image gives four copies; a 1 x N or N x 1 image doubles both axes.
+ * Denormal values are not flushed.  NaN and infinite inputs are unspecified
+ * beyond "no byte outside dst's pixels is written".  rows or cols < 1, a NULL
+ * buffer or context, or a stride too small for its rows: SIFT_E_INVALID; a
+ * dimension above 2^30: SIFT_E_SIZE.  The context's creation limits do not
+ * apply.  Under SIFT_FLAG_PROFILE the stage is "upsample2x" (20 algorithmic
+ * bytes per source pixel).
+ * Host buffers (synchronous): src rows are row_stride_bytes apart (0 = cols * 4;
+ * a multiple of 4) and only the bytes a strided view owns are read; dst is
+ * 2 rows x 2 cols floats, packed: */
+int sift_upsample2x(sift_ctx* ctx, const float* src, int rows, int cols, size_t row_stride_bytes, float* dst);
+/* Device buffers, a batch of images, enqueued on the context stream with no
+ * synchronisation.  Strides in elements (floats), as sift_detect_compute_batch
+ * takes them: out_row_stride >= 2 * cols, and for batch > 1 the image strides
+ * cover an image.  Only the 2 rows x 2 cols pixels of each output image are
+ * written -- row and image padding keep their bytes.  Rows of d_dst that are
+ * 16-byte aligned (d_dst and out_row_stride, and out_img_stride for a batch,
+ * multiples of 4 floats) are written with 16-byte stores. */
+int sift_upsample2x_device(sift_ctx* ctx, const float* d_src, int batch, int rows, int cols, size_t row_stride,
+                           size_t img_stride, float* d_dst, size_t out_row_stride, size_t out_img_stride);
 
 /* ---- matching ------------------------------------------ */
 /* Replaces `BFMatcher(NORM_L1).knnMatch(query, train, matches, k)` of the

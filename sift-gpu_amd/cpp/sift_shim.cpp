@@ -109,9 +109,23 @@ void SIFT_NCL(InputArray image, std::vector<KeyPoint>& keypoints, OutputArray de
   SIFT_NCL(image, Mat(), keypoints, descriptors);
 }
 
-// detectAndCompute's argument order: the mask (CV_8UC1, the image's size, zero
-// = no keypoint here) is applied on the device; an empty mask is no mask.
-void SIFT_NCL(InputArray image, InputArray mask, std::vector<KeyPoint>& keypoints, OutputArray descriptors) {
+namespace {
+
+// sift_set_upsample for the span of one call on the shared context (the
+// context is created for the doubled shape by the caller).
+struct UpsampleScope {
+  sift_ctx* c;
+  bool on;
+  UpsampleScope(sift_ctx* c_, bool on_) : c(c_), on(on_) {
+    if (on) sift_set_upsample(c, 1);
+  }
+  ~UpsampleScope() {
+    if (on) sift_set_upsample(c, 0);
+  }
+};
+
+void detect_and_compute(InputArray image, InputArray mask, std::vector<KeyPoint>& keypoints, OutputArray descriptors,
+                        bool upsample) {
   Mat img = image.getMat();
   require_f32(img, "SIFT_NCL");
   Mat msk = mask.getMat();
@@ -121,7 +135,8 @@ void SIFT_NCL(InputArray image, InputArray mask, std::vector<KeyPoint>& keypoint
       throw std::runtime_error("SIFT_NCL: the mask must have the image's size");
     if (!msk.isContinuous()) throw std::runtime_error("SIFT_NCL: expected a continuous mask");
   }
-  sift_ctx* c = ctx_for(img.rows, img.cols);
+  sift_ctx* c = upsample ? ctx_for(2 * img.rows, 2 * img.cols) : ctx_for(img.rows, img.cols);
+  const UpsampleScope scope(c, upsample);
   int n = 0;
   int rc = sift_detect_compute_masked(c, img.ptr<float>(0), img.rows, img.cols, sizeof(float) * img.cols,
                                       msk.empty() ? nullptr : msk.ptr<unsigned char>(0), (size_t)img.cols, nullptr,
@@ -136,11 +151,20 @@ void SIFT_NCL(InputArray image, InputArray mask, std::vector<KeyPoint>& keypoint
   }
 }
 
-// detectAndCompute(image, mask, keypoints, descriptors, useProvidedKeypoints)
+}  // namespace
+
+// detectAndCompute's argument order: the mask (CV_8UC1, the image's size, zero
+// = no keypoint here) is applied on the device; an empty mask is no mask.
+void SIFT_NCL(InputArray image, InputArray mask, std::vector<KeyPoint>& keypoints, OutputArray descriptors) {
+  detect_and_compute(image, mask, keypoints, descriptors, false);
+}
+
+// detectAndCompute(image, mask, keypoints, descriptors, useProvidedKeypoints),
+// and SIFT::create()'s firstOctave = -1 as `upsample` (sift_set_upsample)
 void SIFT_NCL(InputArray image, InputArray mask, std::vector<KeyPoint>& keypoints, OutputArray descriptors,
-              bool useProvidedKeypoints) {
+              bool useProvidedKeypoints, bool upsample) {
   if (!useProvidedKeypoints) {
-    SIFT_NCL(image, mask, keypoints, descriptors);
+    detect_and_compute(image, mask, keypoints, descriptors, upsample);
     return;
   }
   Mat img = image.getMat();
@@ -149,7 +173,8 @@ void SIFT_NCL(InputArray image, InputArray mask, std::vector<KeyPoint>& keypoint
   descriptors.create(n, SIFT_DESC_LEN, CV_32F);
   if (n == 0) return;
   Mat d = descriptors.getMat();
-  sift_ctx* c = ctx_for(img.rows, img.cols);
+  sift_ctx* c = upsample ? ctx_for(2 * img.rows, 2 * img.cols) : ctx_for(img.rows, img.cols);
+  const UpsampleScope scope(c, upsample);
   int rc = sift_compute(c, img.ptr<float>(0), img.rows, img.cols, sizeof(float) * img.cols,
                         reinterpret_cast<const sift_keypoint*>(keypoints.data()), n, SIFT_N_SCALES - 1,
                         d.ptr<float>(0));

@@ -887,6 +887,49 @@ int sift_bgr8_to_gray(sift_ctx* c, const uint8_t* bgr, int rows, int cols, size_
   return SIFT_OK;
 }
 
+// ---- the doubled image (upsample.hip): cv::resize to twice the size, INTER_LINEAR on CV_32F ----
+int sift_upsample2x_device(sift_ctx* c, const float* d_src, int batch, int rows, int cols, size_t row_stride,
+                           size_t img_stride, float* d_dst, size_t out_row_stride, size_t out_img_stride) {
+  if (!c) return SIFT_E_INVALID;
+  if (!d_src || !d_dst) return fail(c, SIFT_E_INVALID, "null buffer");
+  if (batch < 1 || rows < 1 || cols < 1) return fail(c, SIFT_E_INVALID, "empty image");
+  if (rows > (1 << 30) || cols > (1 << 30)) return fail(c, SIFT_E_SIZE, "the doubled dimensions exceed an int");
+  if (row_stride < (size_t)cols || (batch > 1 && img_stride < row_stride * rows))
+    return fail(c, SIFT_E_INVALID, "source strides too small");
+  if (out_row_stride < (size_t)cols * 2 || (batch > 1 && out_img_stride < out_row_stride * rows * 2))
+    return fail(c, SIFT_E_INVALID, "output strides too small");
+  (void)hipSetDevice(c->device);
+  {
+    StageScope s(c, ST_UPSAMPLE, 0, 20.0 * rows * cols * batch);
+    launch_upsample2x(c->stream, d_src, (long long)row_stride, (long long)img_stride, rows, cols, d_dst,
+                      (long long)out_row_stride, (long long)out_img_stride, batch);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
+int sift_upsample2x(sift_ctx* c, const float* src, int rows, int cols, size_t row_stride_bytes, float* dst) {
+  if (!c) return SIFT_E_INVALID;
+  if (!src || !dst) return fail(c, SIFT_E_INVALID, "null buffer");
+  if (rows < 1 || cols < 1) return fail(c, SIFT_E_INVALID, "empty image");
+  if (rows > (1 << 30) || cols > (1 << 30)) return fail(c, SIFT_E_SIZE, "the doubled dimensions exceed an int");
+  if (row_stride_bytes == 0) row_stride_bytes = (size_t)cols * sizeof(float);
+  if (row_stride_bytes % sizeof(float) || row_stride_bytes < (size_t)cols * sizeof(float))
+    return fail(c, SIFT_E_INVALID, "row stride must be a multiple of 4 bytes and at least cols * 4");
+  (void)hipSetDevice(c->device);
+  const size_t stride = row_stride_bytes / sizeof(float);
+  UpsampleHost S;  // the matcher's scratch doubles as staging here
+  int rc = carve(c, &S, [&](Carver& a) { return upsample_host_layout(a, rows, cols, stride); });
+  if (rc) return rc;
+  // a strided view (an ROI) owns no padding after its last row: copy only what the image owns
+  const size_t owned = ((size_t)(rows - 1) * stride + (size_t)cols) * sizeof(float);
+  HIP_TRY(c, hipMemcpyAsync(S.src, src, owned, hipMemcpyHostToDevice, c->stream));
+  if ((rc = sift_upsample2x_device(c, S.src, 1, rows, cols, stride, 0, S.dst, (size_t)cols * 2, 0))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(dst, S.dst, (size_t)4 * rows * cols * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SIFT_OK;
+}
+
 // ---- findHomography(RANSAC) + perspectiveTransform, src/main.cpp:54-62 ----
 int sift_find_homography(const float* src_xy, const float* dst_xy, int n, double ransac_thresh, int max_iters,
                          double confidence, double* H, unsigned char* inlier_mask) {

@@ -264,6 +264,11 @@ void launch_synth(hipStream_t st, float* out, int batch, int rows, int cols, lon
 
 void launch_bgr8_gray(hipStream_t st, const uint8_t* src, long long sstride, long long simg, int srows, int scols,
                       float* dst, long long dpitch, long long dimg, int drows, int dcols, int batch);
+// upsample.hip: the doubled input image of sift_set_upsample (INTER_LINEAR on
+// CV_32F, the rule at the head of that file); strides in elements.  Writes the
+// 2 rows x 2 cols destination pixels of each image and nothing else.
+void launch_upsample2x(hipStream_t st, const float* src, long long spitch, long long simg, int rows, int cols,
+                       float* dst, long long dpitch, long long dimg, int batch);
 int find_homography_ransac(const float* src_xy, const float* dst_xy, int n, double thr, int max_iters,
                            double confidence, double* H, unsigned char* mask_out);
 void perspective_transform(const double* H, const float* xy, int n, float* out);
@@ -450,8 +455,11 @@ void launch_refine_orient(hipStream_t st, const Layout& L, const float* gpyr, co
 // SparseG4.
 void launch_g4_points(hipStream_t st, const Layout& L, const float* gpyr, const float* coef4, const Cand* pts, int n,
                       float* patch, int grid);
+// half (sift_set_upsample: detection ran on the doubled image): every emitted
+// keypoint has x, y and size multiplied by 0.5f and the low byte of its octave
+// decremented (255 = octave -1) -- OpenCV's post-pass for firstOctave < 0.
 void launch_emit(hipStream_t st, DetectBufs& D, int batch, sift_keypoint* kpts, int kp_cap,
-                 int* img_kp_off);
+                 int* img_kp_off, bool half = false);
 // select.hip: the per-image keypoint budget (sift_set_max_features), between
 // launch_refine_orient and launch_emit.  For every image of the batch whose
 // keypoint count exceeds n_keep, npeaks becomes 0 in each candidate slot whose
@@ -469,11 +477,15 @@ void launch_select_best(hipStream_t st, DetectBufs& D, int batch, int n_keep, bo
 // emitted position rounds (x + 0.5f, y + 0.5f, truncated) to a zero byte or to
 // a pixel outside the image.  bytes == nullptr: nothing is launched.
 // grid_form: launch_select_best's split for one large image.
+// half (sift_set_upsample): the slots hold positions in the doubled image, the
+// mask is the original image's rows x cols: the position is multiplied by 0.5f
+// first, as launch_emit(half) writes it.
 struct DetMask {
   const unsigned char* bytes = nullptr;
   long long row_stride = 0, img_stride = 0;
 };
-void launch_detmask(hipStream_t st, DetectBufs& D, int batch, const DetMask& dm, int rows, int cols, bool grid_form);
+void launch_detmask(hipStream_t st, DetectBufs& D, int batch, const DetMask& dm, int rows, int cols, bool grid_form,
+                    bool half = false);
 // Device status bits; bit i <-> sticky error word err[i] (DescArgs::err_flag = &err[0],
 // status_kernel).
 constexpr int kErrAssert = 1;      // keypoint octave/layer outside the pyramid (CV_Assert)
@@ -491,7 +503,9 @@ void launch_descriptors(hipStream_t st, const Layout& L, const float2* grad, con
                         int* perm);     // [kp_cap] scratch: the lane-balance ranking
 // compute.hip (sift_compute_batch: descriptors at keypoints the caller holds).
 // The prep pass over rows [clamp(off[0]), clamp(off[batch])) of kpts, every
-// offset clamped to [0, kp_cap] (match_seg.hpp): a row with oi < 0,
+// offset clamped to [0, kp_cap] (match_seg.hpp): with oi = octave -
+// first_octave (0, or -1 when L is the doubled image's, sift_set_upsample), a
+// row with oi < 0,
 // oi >= L.n_oct, layer > 4 or layer > max_layer gets 128 zeros in desc and
 // sets err_flag (kErrAssert); every other row goes into one of two index
 // lists -- det: the rows descriptor_kernel's detected-keypoint form can take
@@ -508,11 +522,12 @@ struct DescLists {
   int* counts;  // [2]
 };
 void launch_compute_prep(hipStream_t st, const Layout& L, const sift_keypoint* kpts, const int* off, int batch,
-                         int kp_cap, int max_layer, float* desc, int* err_flag, const DescLists& lists);
-// descriptor.hip: the two descriptor launches over those lists (first_octave 0)
+                         int kp_cap, int max_layer, float* desc, int* err_flag, const DescLists& lists,
+                         int first_octave = 0);
+// descriptor.hip: the two descriptor launches over those lists
 void launch_descriptors_listed(hipStream_t st, const Layout& L, const float2* grad, const MathConsts* mc,
                                const sift_keypoint* kpts, const int* img_kp_off, int batch, int kp_cap, float* desc,
-                               int* err_flag, const DescLists& lists);
+                               int* err_flag, const DescLists& lists, int first_octave = 0);
 void launch_math_selftest(hipStream_t st, int op, const float* a, const float* b, float* out, int n,
                           const MathConsts* mc);
 

@@ -18,7 +18,7 @@ struct PrepArgs {
   Layout L;
   const sift_keypoint* kpts;
   const int* off;  // [batch + 1]
-  int batch, kp_cap, max_layer;
+  int batch, kp_cap, max_layer, first_octave;
   float* desc;
   int* err_flag;
   DescLists lists;
@@ -43,11 +43,13 @@ __global__ __launch_bounds__(kComputeChunk) void compute_prep_kernel(PrepArgs A)
     if (i >= lo && i < hi) {
       const sift_keypoint kp = A.kpts[i];
       // unpackOctave (src/sift.cpp:724-731), as descriptor_kernel reads it; the
-      // pyramid starts at octave 0 (the reference never upsamples)
+      // pyramid starts at octave first_octave: 0 (the reference never
+      // upsamples), or -1 when L is the doubled image's (sift_set_upsample)
       int octave = kp.octave & 255;
       const int layer = (kp.octave >> 8) & 255;
       octave = octave < 128 ? octave : (-128 | octave);
-      if (octave < 0 || octave >= A.L.n_oct || layer > kLayers + 2 || layer > A.max_layer) {
+      const int oi = octave - A.first_octave;
+      if (oi < 0 || oi >= A.L.n_oct || layer > kLayers + 2 || layer > A.max_layer) {
         atomicOr(A.err_flag, 1);
         float4* row = reinterpret_cast<float4*>(A.desc + (long long)i * kDescLen);
         for (int q = 0; q < kDescLen / 4; ++q) row[q] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -55,11 +57,11 @@ __global__ __launch_bounds__(kComputeChunk) void compute_prep_kernel(PrepArgs A)
         // the window radius and the keypoint's pixel by descriptor_kernel's own
         // expressions (its setup after unpackOctave)
         const int d = kDescW;
-        const float scale = 1.f / (1 << octave);
+        const float scale = octave >= 0 ? 1.f / (1 << octave) : (float)(1 << -octave);
         const float size = kp.size * scale;
         const float ptx = kp.x * scale, pty = kp.y * scale;
         const float scl = size * 0.5f;
-        const Octave& O = A.L.oct[octave];
+        const Octave& O = A.L.oct[oi];
         const int rows = O.rows, cols = O.cols;
         const int px = cv_round(ptx), py = cv_round(pty);
         const float hist_width = 3.f * scl;
@@ -102,7 +104,8 @@ __global__ __launch_bounds__(kComputeChunk) void compute_prep_kernel(PrepArgs A)
 }  // namespace
 
 void launch_compute_prep(hipStream_t st, const Layout& L, const sift_keypoint* kpts, const int* off, int batch,
-                         int kp_cap, int max_layer, float* desc, int* err_flag, const DescLists& lists) {
+                         int kp_cap, int max_layer, float* desc, int* err_flag, const DescLists& lists,
+                         int first_octave) {
   if (kp_cap <= 0) return;
   (void)hipMemsetAsync(lists.counts, 0, 2 * sizeof(int), st);
   PrepArgs A;
@@ -112,6 +115,7 @@ void launch_compute_prep(hipStream_t st, const Layout& L, const sift_keypoint* k
   A.batch = batch;
   A.kp_cap = kp_cap;
   A.max_layer = max_layer;
+  A.first_octave = first_octave;
   A.desc = desc;
   A.err_flag = err_flag;
   A.lists = lists;

@@ -458,6 +458,12 @@ int sift_set_max_features(sift_ctx* c, int n_per_image) {
   return SIFT_OK;
 }
 
+int sift_set_upsample(sift_ctx* c, int on) {
+  if (!c) return SIFT_E_INVALID;
+  c->upsample = on != 0;  // part of the SIFT_NCL and sift_compute graph keys, like the budget
+  return SIFT_OK;
+}
+
 int sift_set_candidate_capacity(sift_ctx* c, int per_image) {
   if (!c) return SIFT_E_INVALID;
   if (per_image < 1 || (long long)per_image * c->max_batch > (1ll << 30))

@@ -61,7 +61,7 @@ class Buf {
   X(ST_MATCH_L2_U8, "match_l2sqr_u8_segmented") X(ST_SELECT, "select_best")                               \
   X(ST_CROSS, "cross_check_matches") X(ST_DETMASK, "detect_mask") X(ST_GRAD, "gradient")                \
   X(ST_COMPUTE_PREP, "compute_prep") X(ST_WINDOW_BIN, "match_window_bin")                              \
-  X(ST_MATCH_WINDOW, "match_window_segmented")
+  X(ST_MATCH_WINDOW, "match_window_segmented") X(ST_UPSAMPLE, "upsample2x")
 enum Stage {
 #define X(id, name) id,
   SIFT_STAGES(X)
@@ -131,6 +131,12 @@ struct sift_ctx {
   // packed (rows cols bytes apart): max_rows x max_cols bytes, allocated by the
   // first masked host call and never moved, so captured sequences may name it
   sift::Buf<unsigned char> d_detmask;
+  // sift_set_upsample (upsample.hip): with it on, SIFT_NCL and sift_compute[_batch]
+  // double each image into d_up -- laid out like d_in (in_pitch, in_img; the
+  // pitch check_fast is asked about), max_batch images, allocated by the first
+  // upsampled call and never moved, so captured sequences may name it
+  bool upsample = false;
+  sift::Buf<float> d_up;
   sift::DetectBufs D{};
   int blk_cap = 0;
   sift::Buf<int> d_img_off;       // [max_batch+1] for the host entry points

@@ -943,7 +943,7 @@ void launch_descriptors(hipStream_t st, const Layout& L, const float2* grad, con
 // not in layer order, and an empty list costs one launch of waves that exit.
 void launch_descriptors_listed(hipStream_t st, const Layout& L, const float2* grad, const MathConsts* mc,
                                const sift_keypoint* kpts, const int* img_kp_off, int batch, int kp_cap, float* desc,
-                               int* err_flag, const DescLists& lists) {
+                               int* err_flag, const DescLists& lists, int first_octave) {
   if (kp_cap <= 0) return;
   DescArgs A;
   A.L = L;
@@ -955,7 +955,7 @@ void launch_descriptors_listed(hipStream_t st, const Layout& L, const float2* gr
   A.batch = batch;
   A.kp_cap = kp_cap;
   A.desc = desc;
-  A.first_octave = 0;
+  A.first_octave = first_octave;
   A.err_flag = err_flag;
   A.list = lists.det;
   A.list_n = lists.counts;

@@ -1803,6 +1803,11 @@ void launch_g4_points(hipStream_t st, const Layout& L, const float* gpyr, const 
 }
 
 // ---- ordered keypoint emission ------------------------------------------------
+// HALF (sift_set_upsample): the candidates are the doubled image's; the
+// keypoint goes out in the original image's frame -- x, y and size times 0.5f
+// (exact) and the octave byte one lower, 255 for octave -1 -- which is what
+// SIFT::detectAndCompute does to every keypoint when firstOctave < 0.
+template <bool HALF>
 __global__ __launch_bounds__(256) void emit_kernel(const CandOut* __restrict__ couts,
                                                    const int* __restrict__ kp_scan,
                                                    const int* __restrict__ cand_total, int cand_cap,
@@ -1818,12 +1823,12 @@ __global__ __launch_bounds__(256) void emit_kernel(const CandOut* __restrict__ c
       const int pos = base + k;
       if (pos >= kp_cap) break;
       sift_keypoint kp;
-      kp.x = co.x;
-      kp.y = co.y;
-      kp.size = co.size;
+      kp.x = HALF ? co.x * 0.5f : co.x;
+      kp.y = HALF ? co.y * 0.5f : co.y;
+      kp.size = HALF ? co.size * 0.5f : co.size;
       kp.angle = co.angle[k];
       kp.response = co.response;
-      kp.octave = co.octave;
+      kp.octave = HALF ? (co.octave & ~255) | ((co.octave - 1) & 255) : co.octave;
       kp.class_id = -1;
       kpts[pos] = kp;
     }
@@ -1858,12 +1863,16 @@ void launch_status(hipStream_t st, const int* cand_total, int cand_cap, const in
 }
 
 void launch_emit(hipStream_t st, DetectBufs& D, int batch, sift_keypoint* kpts, int kp_cap,
-                 int* img_kp_off) {
+                 int* img_kp_off, bool half) {
   // kp_scan = exclusive scan of npeaks over the (clamped) candidate list
   launch_scan(st, D.npeaks, D.kp_scan, D.cand_total, 0, D.cand_cap, D.kp_total, D.scan_tiles,
               ScanGather{D.img_cand_off, 0, batch, img_kp_off});
-  hipLaunchKernelGGL(emit_kernel, dim3(1024), dim3(256), 0, st, D.couts, D.kp_scan, D.cand_total,
-                     D.cand_cap, kpts, kp_cap);
+  if (half)
+    hipLaunchKernelGGL(emit_kernel<true>, dim3(1024), dim3(256), 0, st, D.couts, D.kp_scan, D.cand_total,
+                       D.cand_cap, kpts, kp_cap);
+  else
+    hipLaunchKernelGGL(emit_kernel<false>, dim3(1024), dim3(256), 0, st, D.couts, D.kp_scan, D.cand_total,
+                       D.cand_cap, kpts, kp_cap);
 }
 
 }  // namespace sift

@@ -15,6 +15,9 @@
 // coordinate, drops the slot; that test comes first, so no byte outside the
 // image's rows x cols is ever read.  The scan, the emission and the descriptor
 // pass that follow see a shorter list -- same order, same bytes per keypoint.
+// With sift_set_upsample the slots hold positions in the doubled image and the
+// mask stays the original image's: x and y are multiplied by 0.5f (exact)
+// before the rule, which is then the rule on the emitted coordinates.
 //
 // One byte gather per live slot; the slots of an image are strided over by
 // `parts` workgroups (1 for a batch's ~10^4 slots per image, more for one large
@@ -32,7 +35,7 @@ constexpr int kDetMaskT = 256;
 
 __global__ __launch_bounds__(kDetMaskT) void detmask_kernel(const CandOut* __restrict__ couts, int* npeaks,
                                                             const int* __restrict__ img_cand_off, int cand_cap,
-                                                            DetMask dm, int rows, int cols) {
+                                                            DetMask dm, int rows, int cols, float pos_scale) {
   const int b = blockIdx.x;
   int lo = img_cand_off[b], hi = img_cand_off[b + 1];
   lo = lo < 0 ? 0 : lo < cand_cap ? lo : cand_cap;
@@ -42,7 +45,8 @@ __global__ __launch_bounds__(kDetMaskT) void detmask_kernel(const CandOut* __res
   const float frows = (float)rows, fcols = (float)cols;  // exact: the dimensions are far below 2^24
   for (long long ci = (long long)lo + blockIdx.y * kDetMaskT + threadIdx.x; ci < hi; ci += stride) {
     if (npeaks[ci] <= 0) continue;
-    const float fx = couts[ci].x + 0.5f, fy = couts[ci].y + 0.5f;
+    // pos_scale: 1.f, or 0.5f (exact) for candidates of the doubled image -- the emitted position
+    const float fx = couts[ci].x * pos_scale + 0.5f, fy = couts[ci].y * pos_scale + 0.5f;
     // the range test on the floats, before the conversion: a NaN fails every
     // comparison, and (int) is taken only of a value in (-1, cols) / (-1, rows)
     bool keep = fx > -1.0f && fx < fcols && fy > -1.0f && fy < frows;
@@ -53,12 +57,13 @@ __global__ __launch_bounds__(kDetMaskT) void detmask_kernel(const CandOut* __res
 
 }  // namespace
 
-void launch_detmask(hipStream_t st, DetectBufs& D, int batch, const DetMask& dm, int rows, int cols, bool grid_form) {
+void launch_detmask(hipStream_t st, DetectBufs& D, int batch, const DetMask& dm, int rows, int cols, bool grid_form,
+                    bool half) {
   if (!dm.bytes || batch < 1) return;
   // launch_select_best's split: eight strides of a workgroup over the whole list at most
   const int parts = grid_form ? std::min(1024, std::max(1, (D.cand_cap + kDetMaskT * 8 - 1) / (kDetMaskT * 8))) : 1;
   hipLaunchKernelGGL(detmask_kernel, dim3(batch, parts), dim3(kDetMaskT), 0, st, D.couts, D.npeaks, D.img_cand_off,
-                     D.cand_cap, dm, rows, cols);
+                     D.cand_cap, dm, rows, cols, half ? 0.5f : 1.f);
 }
 
 }  // namespace sift

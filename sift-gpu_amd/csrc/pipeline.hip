@@ -3,6 +3,7 @@
 // memory, the six sub-module entry points, and the test helpers.  Host code
 // and one test kernel; the kernels live in blur.hip, pyramid_pc.hip,
 // detect.hip and descriptor.hip.
+#include <limits.h>
 #include <math.h>
 #include <stdio.h>
 
@@ -42,6 +43,26 @@ double octave_taps(const sift_ctx* c, bool two_d, int n = 4) {
   double taps = 0;
   for (int q = 0; q < n; ++q) taps += two_d ? (double)(2 * c->wsz[q] + 1) * (2 * c->wsz[q] + 1) : 2 * c->wsz[q] + 1;
   return taps;
+}
+
+// sift_set_upsample: SIFT_NCL and sift_compute[_batch] run on the doubled image.
+// run_dim is the dimension the entry points check against the context's limits
+// (one that cannot be doubled in an int is above every limit; a non-positive
+// one is passed through for check_dims to refuse).
+int run_dim(const sift_ctx* c, int v) { return !c->upsample || v <= 0 ? v : v > (1 << 30) ? INT_MAX : 2 * v; }
+
+// The doubled images' buffer, laid out like d_in; allocated once, never moved.
+int ensure_up(sift_ctx* c) {
+  if (!c->d_up.get() && c->d_up.grow((size_t)c->in_img * c->max_batch) != hipSuccess)
+    return fail(c, SIFT_E_NOMEM, "upsampled image buffer");
+  return SIFT_OK;
+}
+
+// Doubles the batch's images into d_up (upsample.hip) and returns that plane.
+Plane enqueue_upsample(sift_ctx* c, Plane src, int batch, int rows, int cols) {
+  StageScope s(c, ST_UPSAMPLE, 0, 20.0 * rows * cols * batch);
+  launch_upsample2x(c->stream, src.p, src.pitch, src.img_stride, rows, cols, c->d_up, c->in_pitch, c->in_img, batch);
+  return Plane{c->d_up, c->in_pitch, c->in_img};
 }
 
 void enqueue_decimate(sift_ctx* c, const Layout& L, int o, int batch) {
@@ -163,9 +184,12 @@ void enqueue_pyramid(sift_ctx* c, const Layout& L, Plane src, int batch, bool wi
 // dm.bytes != nullptr (the *_masked calls only): after the budget, as OpenCV
 // orders retainBest and runByPixelsMask, every keypoint on a zero byte of the
 // image's detection mask is dropped as well (detmask.hip).
+// half (sift_set_upsample; L is the doubled image's): keypoints are emitted in
+// the original image's frame, and the mask, which is that image's size, is
+// read at those coordinates.
 void enqueue_detect(sift_ctx* c, const Layout& L, int batch, sift_keypoint* kpts, int kp_cap,
                     int* img_off, bool dog_from_gpyr, unsigned sparse = 0, int max_features = 0,
-                    const DetMask& dm = DetMask{}) {
+                    const DetMask& dm = DetMask{}, bool half = false) {
   hipStream_t st = c->stream;
   {
     StageScope s(c, ST_EXTREMA);
@@ -183,11 +207,12 @@ void enqueue_detect(sift_ctx* c, const Layout& L, int batch, sift_keypoint* kpts
   }
   if (dm.bytes) {
     StageScope s(c, ST_DETMASK);
-    launch_detmask(st, c->D, batch, dm, L.rows, L.cols, c->D.cand_cap / c->max_batch > c->select_block_max);
+    launch_detmask(st, c->D, batch, dm, half ? L.rows / 2 : L.rows, half ? L.cols / 2 : L.cols,
+                   c->D.cand_cap / c->max_batch > c->select_block_max, half);
   }
   {
     StageScope s(c, ST_EMIT);
-    launch_emit(st, c->D, batch, kpts, kp_cap, img_off);
+    launch_emit(st, c->D, batch, kpts, kp_cap, img_off, half);
   }
 }
 
@@ -240,9 +265,14 @@ void verbose_phase(sift_ctx* c, const char* what, hipEvent_t a, hipEvent_t b) {
 int enqueue_ncl(sift_ctx* c, const float* d_imgs, int batch, int rows, int cols, size_t row_stride,
                 size_t img_stride, sift_keypoint* d_kpts, float* d_desc, int kp_cap, int* d_img_offsets,
                 const DetMask& dm = DetMask{}) {
-  const Layout L = make_layout(rows, cols, c->n_oct);
-  const Plane src{d_imgs, (long long)row_stride, (long long)img_stride};
-  if (int rc = check_fast(c, L, (long long)row_stride)) return rc;
+  // sift_set_upsample: the same sequence on the doubled images (rows, cols stay
+  // the caller's, which is what the mask and the key are about)
+  const bool up = c->upsample;
+  const Layout L = make_layout(up ? 2 * rows : rows, up ? 2 * cols : cols, c->n_oct);
+  const Plane in{d_imgs, (long long)row_stride, (long long)img_stride};
+  if (up)
+    if (int rc = ensure_up(c)) return rc;
+  if (int rc = check_fast(c, L, up ? c->in_pitch : (long long)row_stride)) return rc;
   // detection yields at most kMaxPeaks keypoints per candidate slot, so the
   // ranking scratch never needs more than that, whatever kp_cap the caller gives
   if (int rc = ensure_perm(c, (int)std::min<long long>(kp_cap, (long long)kMaxPeaks * c->D.cand_cap))) return rc;
@@ -256,11 +286,13 @@ int enqueue_ncl(sift_ctx* c, const float* d_imgs, int batch, int rows, int cols,
   };
   auto body = [&]() {
     mark(0);
+    const Plane src = up ? enqueue_upsample(c, in, batch, rows, cols) : in;
     enqueue_pyramid(c, L, src, batch, false, sparse);
     mark(1);
-    enqueue_detect(c, L, batch, d_kpts, kp_cap, d_img_offsets, true, sparse, c->max_features, dm);
+    enqueue_detect(c, L, batch, d_kpts, kp_cap, d_img_offsets, true, sparse, c->max_features, dm, up);
     mark(2);
-    enqueue_desc(c, L, d_kpts, d_img_offsets, batch, kp_cap, d_desc, 0, true);
+    // the doubled pyramid's first octave is -1: unpackOctave maps the emitted rows back onto it
+    enqueue_desc(c, L, d_kpts, d_img_offsets, batch, kp_cap, d_desc, up ? -1 : 0, true);
     mark(3);
     enqueue_status(c, true, d_img_offsets, batch, kp_cap);
   };
@@ -277,7 +309,7 @@ int enqueue_ncl(sift_ctx* c, const float* d_imgs, int batch, int rows, int cols,
   // sequence id 1, then everything that shapes the sequence; stall_once is the
   // test hook: a captured poll bound must not be replayed
   key_put(key, 1, batch, rows, cols, row_stride, img_stride, kp_cap, c->n_oct, c->flags, c->stall_once, sparse,
-          c->max_features, dm.bytes != nullptr, dm.row_stride, dm.img_stride);
+          c->max_features, dm.bytes != nullptr, dm.row_stride, dm.img_stride, up);
   key_put(ptrs, d_imgs, dm.bytes, d_kpts, d_desc, d_img_offsets);
   return run_graphed(c, key, ptrs, body);
 }
@@ -296,9 +328,15 @@ int compute_perm_ints(int kp_cap) { return 2 * kp_cap + 2; }
 int enqueue_compute(sift_ctx* c, const float* d_imgs, int batch, int rows, int cols, size_t row_stride,
                     size_t img_stride, const sift_keypoint* d_kpts, const int* d_kp_offsets, int kp_cap, int max_layer,
                     float* d_desc) {
-  const Layout L = make_layout(rows, cols, c->n_oct);
-  const Plane src{d_imgs, (long long)row_stride, (long long)img_stride};
-  if (int rc = check_fast(c, L, (long long)row_stride)) return rc;
+  // sift_set_upsample: the doubled images' pyramid, whose first octave is -1;
+  // the rows stay in the original image's frame (unpackOctave scales them)
+  const bool up = c->upsample;
+  const Layout L = make_layout(up ? 2 * rows : rows, up ? 2 * cols : cols, c->n_oct);
+  const Plane in{d_imgs, (long long)row_stride, (long long)img_stride};
+  const int first_octave = up ? -1 : 0;
+  if (up)
+    if (int rc = ensure_up(c)) return rc;
+  if (int rc = check_fast(c, L, up ? c->in_pitch : (long long)row_stride)) return rc;
   if (int rc = ensure_perm(c, compute_perm_ints(kp_cap))) return rc;
   unsigned skip4 = 0;
   if (max_layer < kScales - 1 && !(c->flags & SIFT_FLAG_FAST))
@@ -306,6 +344,7 @@ int enqueue_compute(sift_ctx* c, const float* d_imgs, int batch, int rows, int c
       if (use_sym_blur(c, L.oct[o].rows, L.oct[o].cols, batch)) skip4 |= 1u << o;
   const DescLists lists{c->d_perm, c->d_perm + kp_cap, c->d_perm + 2 * (size_t)kp_cap};
   auto body = [&]() {
+    const Plane src = up ? enqueue_upsample(c, in, batch, rows, cols) : in;
     enqueue_pyramid(c, L, src, batch, false, skip4);
     {
       StageScope s(c, ST_GRAD, 0, 12.0 * (max_layer + 1) * (double)L.g_img / kScales * batch);
@@ -313,17 +352,18 @@ int enqueue_compute(sift_ctx* c, const float* d_imgs, int batch, int rows, int c
     }
     {
       StageScope s(c, ST_COMPUTE_PREP, 0, 36.0 * kp_cap);
-      launch_compute_prep(c->stream, L, d_kpts, d_kp_offsets, batch, kp_cap, max_layer, d_desc, c->d_err, lists);
+      launch_compute_prep(c->stream, L, d_kpts, d_kp_offsets, batch, kp_cap, max_layer, d_desc, c->d_err, lists,
+                          first_octave);
     }
     {
       StageScope s(c, ST_DESC);
       launch_descriptors_listed(c->stream, L, c->d_grad, c->d_mc, d_kpts, d_kp_offsets, batch, kp_cap, d_desc,
-                                c->d_err, lists);
+                                c->d_err, lists, first_octave);
     }
     enqueue_status(c, false, nullptr, batch, kp_cap);  // no detection ran: assertion (and stall) bits only
   };
   std::vector<char> key, ptrs;
-  key_put(key, 2, batch, rows, cols, row_stride, img_stride, kp_cap, c->n_oct, c->flags, c->stall_once, max_layer);
+  key_put(key, 2, batch, rows, cols, row_stride, img_stride, kp_cap, c->n_oct, c->flags, c->stall_once, max_layer, up);
   key_put(ptrs, d_imgs, d_kpts, d_kp_offsets, d_desc);
   return run_graphed(c, key, ptrs, body);
 }
@@ -446,7 +486,7 @@ int sift_detect_compute_batch_masked(sift_ctx* c, const float* d_imgs, int batch
                                      size_t mask_row_stride, size_t mask_img_stride, sift_keypoint* d_kpts,
                                      float* d_desc, int kp_cap, int* d_img_offsets) {
   if (!c) return SIFT_E_INVALID;
-  int rc = check_dims(c, rows, cols, c->n_oct, batch);
+  int rc = check_dims(c, run_dim(c, rows), run_dim(c, cols), c->n_oct, batch);
   if (rc) return rc;
   if (!d_imgs || !d_kpts || !d_desc || !d_img_offsets || kp_cap < 0 || row_stride < (size_t)cols)
     return fail(c, SIFT_E_INVALID, "null buffer or bad stride");
@@ -478,7 +518,7 @@ int sift_detect_compute_masked(sift_ctx* c, const float* img, int rows, int cols
   if (!img || !n_out) return fail(c, SIFT_E_INVALID, "null image or n_out");
   if (row_stride_bytes == 0) row_stride_bytes = (size_t)cols * sizeof(float);
   if (mask_row_stride_bytes == 0) mask_row_stride_bytes = (size_t)(cols > 0 ? cols : 0);
-  if (int rc = check_dims(c, rows, cols, c->n_oct, 1)) return rc;
+  if (int rc = check_dims(c, run_dim(c, rows), run_dim(c, cols), c->n_oct, 1)) return rc;
   if (mask && mask_row_stride_bytes < (size_t)cols) return fail(c, SIFT_E_INVALID, "mask_row_stride_bytes < cols");
   (void)hipSetDevice(c->device);
   if (mask && !c->d_detmask.get() &&
@@ -516,7 +556,7 @@ int sift_compute_batch(sift_ctx* c, const float* d_imgs, int batch, int rows, in
   if (batch == 0 || kp_cap == 0) return SIFT_OK;  // no row to describe
   if (!d_imgs || !d_kpts || !d_kp_offsets || !d_desc || row_stride < (size_t)(cols > 0 ? cols : 0))
     return fail(c, SIFT_E_INVALID, "null buffer or bad stride");
-  if (int rc = check_dims(c, rows, cols, c->n_oct, batch)) return rc;
+  if (int rc = check_dims(c, run_dim(c, rows), run_dim(c, cols), c->n_oct, batch)) return rc;
   if (kp_cap > kMaxComputeRows) return fail(c, SIFT_E_SIZE, "kp_cap above 2^30 rows");
   (void)hipSetDevice(c->device);
   c->last_n = -1;
@@ -536,7 +576,7 @@ int sift_compute(sift_ctx* c, const float* img, int rows, int cols, size_t row_s
   if (n == 0) return SIFT_OK;
   if (!img || !kpts || !desc) return fail(c, SIFT_E_INVALID, "null buffer");
   if (row_stride_bytes == 0) row_stride_bytes = (size_t)(cols > 0 ? cols : 0) * sizeof(float);
-  if (int rc = check_dims(c, rows, cols, c->n_oct, 1)) return rc;
+  if (int rc = check_dims(c, run_dim(c, rows), run_dim(c, cols), c->n_oct, 1)) return rc;
   if (n > kMaxComputeRows) return fail(c, SIFT_E_SIZE, "more than 2^30 keypoints");
   (void)hipSetDevice(c->device);
   if (int rc = ensure_kp(c, n)) return rc;

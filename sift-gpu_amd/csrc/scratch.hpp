@@ -273,6 +273,12 @@ inline BgrHost bgr_host_layout(Carver& a, int rows, size_t row_stride, int out_r
   return {a.take<uint8_t>((size_t)rows * row_stride), a.take<float>((size_t)out_rows * out_cols)};
 }
 
+// sift_upsample2x: the strided source rows (in floats), then the packed doubled image.
+struct UpsampleHost { float* src; float* dst; };
+inline UpsampleHost upsample_host_layout(Carver& a, int rows, int cols, size_t row_stride) {
+  return {a.take<float>((size_t)rows * row_stride), a.take<float>((size_t)4 * rows * cols)};
+}
+
 // sift_find_homography_segmented_device (homography_batch.hip): per segment one
 // round of kHomogRound hypotheses -- the accepted 4-point subsets, their models
 // and inlier counts (-1: no model) -- then the state the RANSAC kernel hands to

@@ -91,6 +91,9 @@ def lib():
             "sift_sync": (ip, [vp]),
             "sift_set_candidate_capacity": (ip, [vp, ip]),
             "sift_set_max_features": (ip, [vp, ip]),
+            "sift_set_upsample": (ip, [vp, ip]),
+            "sift_upsample2x": (ip, [vp, fp, ip, ip, sz, fp]),
+            "sift_upsample2x_device": (ip, [vp, vp, ip, ip, ip, sz, sz, vp, sz, sz]),
             "sift_version": (ctypes.c_char_p, []),
             "sift_graph_stats": (ip, [vp, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong),
                                       ctypes.POINTER(ctypes.c_longlong)]),
@@ -173,7 +176,8 @@ def lib():
         optional = {"sift_graph_stats", "sift_g4_fill_stats", "sift_set_max_features",
                     "sift_multi_set_max_features", "sift_detect_compute_masked", "sift_detect_compute_batch_masked",
                     "sift_multi_step_masked", "sift_compute_batch", "sift_compute",
-                    "sift_knn_match_window_segmented_device", "sift_knn_match_window_segmented"}  # absent from older builds (A/B runs against a saved library)
+                    "sift_knn_match_window_segmented_device", "sift_knn_match_window_segmented",
+                    "sift_set_upsample", "sift_upsample2x", "sift_upsample2x_device"}  # absent from older builds (A/B runs against a saved library)
         for name, (res, args) in sigs.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -304,9 +308,37 @@ class Context:
         order (cv::KeyPointsFilter::retainBest; include/sift_hip.h)."""
         self._check("sift_set_max_features", self._L.sift_set_max_features(self.h, n))
 
+    def set_upsample(self, on: bool):
+        """The upsampled first octave (SIFT::create()'s firstOctave = -1; sift_set_upsample in
+        include/sift_hip.h): SIFT_NCL, detect_compute_batch, compute and compute_batch double each
+        image on the device and run on that; keypoints come out in the original image's frame with
+        octave bytes from 255 (octave -1) up.  The context must hold the doubled shape."""
+        self._check("sift_set_upsample", self._L.sift_set_upsample(self.h, int(bool(on))))
+        self._upsample = bool(on)
+
+    class _UpsampleCall:
+        """upsample=True of one call: the setting on for its span, then as it was."""
+
+        def __init__(self, ctx, on):
+            self.ctx, self.flip = ctx, bool(on) and not getattr(ctx, "_upsample", False)
+
+        def __enter__(self):
+            if self.flip:
+                self.ctx.set_upsample(True)
+
+        def __exit__(self, *a):
+            if self.flip:
+                self.ctx.set_upsample(False)
+
     # ---- host-memory API (reference names) ------------------------------
+    def SIFT_NCL_upsampled(self, img: np.ndarray, row_stride_bytes: int | None = None, mask=None, keypoints=None):
+        """SIFT_NCL with set_upsample(True) for the span of this call (then the setting as it was)."""
+        with self._UpsampleCall(self, True):
+            return self.SIFT_NCL(img, row_stride_bytes, mask, keypoints)
+
     def SIFT_NCL(self, img: np.ndarray, row_stride_bytes: int | None = None, mask=None, keypoints=None):
-        """keypoints given (detectAndCompute's useProvidedKeypoints): they are described
+        """Runs under the context's set_upsample setting (SIFT_NCL_upsampled: on for one call).
+        keypoints given (detectAndCompute's useProvidedKeypoints): they are described
         unchanged -- (keypoints, self.compute(img, keypoints)) -- and the mask is
         ignored, as OpenCV ignores it.  Otherwise:
         row_stride_bytes None: img is copied to a contiguous float32 array.
@@ -388,19 +420,41 @@ class Context:
             self._check("sift_copy_results", rc)
         return kps
 
-    def compute(self, img: np.ndarray, keypoints: np.ndarray, max_layer: int = 4) -> np.ndarray:
+    def compute(self, img: np.ndarray, keypoints: np.ndarray, max_layer: int = 4,
+                upsample: bool = False) -> np.ndarray:
         """Feature2D::compute: the descriptors [n, 128] of img at the given keypoints
         (KEYPOINT_DTYPE rows, unchanged), in the pyramid SIFT_NCL builds for img.
         max_layer: no keypoint names a scale above it (3 for detected keypoints
-        spares the widest blur).  A row outside the pyramid raises SiftError."""
+        spares the widest blur).  A row outside the pyramid raises SiftError.
+        upsample True: set_upsample(True) for this call -- the doubled image's
+        pyramid, keypoints in img's own frame, octave -1 (byte 255) valid."""
         img = np.ascontiguousarray(img, np.float32)
         kps = np.ascontiguousarray(keypoints, KEYPOINT_DTYPE).reshape(-1)
         r, c = img.shape
         desc = np.zeros((len(kps), DESC_LEN), np.float32)
-        self._check("sift_compute",
-                    self._L.sift_compute(self.h, _fp(img), r, c, c * 4, kps.ctypes.data, len(kps), max_layer,
-                                         _fp(desc)))
+        with self._UpsampleCall(self, upsample):
+            rc = self._L.sift_compute(self.h, _fp(img), r, c, c * 4, kps.ctypes.data, len(kps), max_layer, _fp(desc))
+        self._check("sift_compute", rc)
         return desc
+
+    def upsample2x(self, img: np.ndarray) -> np.ndarray:
+        """img doubled along both axes: cv::resize(img, (2 * cols, 2 * rows), INTER_LINEAR) on
+        float32 by the rule in include/sift_hip.h (sift_upsample2x); [2 * rows, 2 * cols] float32."""
+        img = np.ascontiguousarray(img, np.float32)
+        if img.ndim != 2:
+            raise ValueError("expected a 2-D image")
+        r, c = img.shape
+        out = np.empty((2 * r, 2 * c), np.float32)
+        self._check("sift_upsample2x", self._L.sift_upsample2x(self.h, _fp(img), r, c, c * 4, _fp(out)))
+        return out
+
+    def upsample2x_device(self, src_ptr: int, batch: int, rows: int, cols: int, row_stride: int, img_stride: int,
+                          dst_ptr: int, out_row_stride: int, out_img_stride: int):
+        """Device-pointer form (no sync) for a batch; strides in elements (floats)."""
+        self._check("sift_upsample2x_device",
+                    self._L.sift_upsample2x_device(self.h, ctypes.c_void_p(src_ptr), batch, rows, cols, row_stride,
+                                                   img_stride, ctypes.c_void_p(dst_ptr), out_row_stride,
+                                                   out_img_stride))
 
     def calDescriptor(self, gpyr, keypoints: np.ndarray, firstOctave: int = 0) -> np.ndarray:
         r, c = gpyr[0].shape
@@ -1072,6 +1126,11 @@ def _ctx(rows, cols):
     return _default
 
 
+def _ctx_for(image, upsample):
+    r, c = np.shape(image)
+    return _ctx(2 * r, 2 * c) if upsample else _ctx(r, c)  # the doubled image must fit the context
+
+
 def SIFT_NCL(image, mask=None, keypoints=None):
     """mask: detectAndCompute's mask (uint8 or bool, the image's shape; zero = no keypoint here).
     keypoints: useProvidedKeypoints -- describe these and detect nothing; the mask is ignored."""
@@ -1081,9 +1140,18 @@ def SIFT_NCL(image, mask=None, keypoints=None):
     return _ctx(*image.shape).SIFT_NCL(image, mask=mask)
 
 
-def compute(image, keypoints):
-    """Feature2D::compute(image, keypoints): the [n, 128] descriptors at the given keypoints."""
-    return _ctx(*np.shape(image)).compute(image, keypoints)
+def SIFT_NCL_upsampled(image, mask=None, keypoints=None):
+    """SIFT_NCL with SIFT::create()'s firstOctave = -1: the image is doubled on the device first
+    and the keypoints come back in its own frame, octave bytes from 255 (octave -1) up."""
+    if keypoints is None:
+        mask = _detection_mask(mask, np.shape(image))
+    return _ctx_for(image, True).SIFT_NCL_upsampled(image, mask=mask, keypoints=keypoints)
+
+
+def compute(image, keypoints, upsample=False):
+    """Feature2D::compute(image, keypoints): the [n, 128] descriptors at the given keypoints
+    (upsample: in the doubled image's pyramid, octave -1 valid)."""
+    return _ctx_for(image, upsample).compute(image, keypoints, upsample=upsample)
 
 
 def Gaussian_Blur(src, sigma):

@@ -1,12 +1,16 @@
 // apps.hip -- the application stages behind the C ABI (include/sift_hip.h):
-// the L1 kNN matcher, its segmented form, the byte quantiser and the byte matchers (L1, squared L2),
-// the ratio test with point pairs, the cross-check stage (cross_check.hip) with its one-call form
-// and the BGR8 front end, each in a device and a
-// host form, the one-pair homography
-// wrappers and the segmented homography and corner transform.  Host code only;
-// the kernels live in match.hip, match_u8.hip, match_l2_u8.hip, frontend.hip and homography_batch.hip (the
-// one-pair homography is host code in homography.hip).  Every form carves its scratch from the context's one block
-// by a layout of scratch.hpp.
+// the L1 kNN matcher, the byte quantiser, the three segmented matchers (float
+// L1, byte L1, byte squared L2), the windowed matcher, the ratio test with
+// point pairs, the cross-check stage with its one-call form, the BGR8 front
+// end and the doubled image, each in a device and a host form, the one-pair
+// homography wrappers and the segmented homography and corner transform.  Host
+// code only; the kernels live in match.hip, match_u8.hip, match_l2_u8.hip,
+// match_window.hip, cross_check.hip, frontend.hip, upsample.hip and
+// homography_batch.hip (the one-pair homography is host code in
+// homography.hip).  The segmented matchers are one path, written once as
+// function templates over a metric tag (MatchL1F32, MatchL1U8, MatchL2SqrU8);
+// their extern "C" entry points only forward.  Every form carves its scratch
+// from the context's one block by a layout of scratch.hpp.
 #include "ctx.hpp"
 #include "scratch.hpp"
 
@@ -32,19 +36,67 @@ int carve(sift_ctx* c, S* out, F&& layout) {
   return SIFT_OK;
 }
 
-bool rows_aligned(const float* query, const float* train) {
-  return !((reinterpret_cast<uintptr_t>(query) | reinterpret_cast<uintptr_t>(train)) & 15);
+bool aligned16(const void* a, const void* b) {
+  return !((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15);
 }
 const char* const kRowsUnaligned = "descriptor rows must be 16-byte aligned";
 
 int clamp_off(int v, int cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
+
+bool known_metric(int metric) {
+  return metric == SIFT_METRIC_L1_F32 || metric == SIFT_METRIC_L1_U8 || metric == SIFT_METRIC_L2SQR_U8;
+}
+const char* const kBadMetric = "metric must be one of SIFT_METRIC_L1_F32, _L1_U8, _L2SQR_U8";
+
+// Rows [clamp(q_offsets[0]), clamp(q_offsets[n_segments])) of a [q_cap][k]
+// result come back: the others are left untouched, as in the device form.
+int copy_back_live_rows(sift_ctx* c, const int* q_offsets, int n_segments, int q_cap, int k, int* idx, float* dist,
+                        const int* d_idx, const float* d_dist) {
+  const int lo = clamp_off(q_offsets[0], q_cap), hi = clamp_off(q_offsets[n_segments], q_cap);
+  if (hi > lo) {
+    const size_t n = (size_t)(hi - lo) * k, o = (size_t)lo * k;
+    HIP_TRY(c, hipMemcpyAsync(idx + o, d_idx + o, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dist + o, d_dist + o, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SIFT_OK;
+}
+
+// The match offsets come back first; then only the written records, with their
+// point pairs when the caller asked for them.
+int copy_back_records(sift_ctx* c, int n_segments, int m_cap, bool pairs, int* m_offsets, const int* d_m_off,
+                      sift_match* matches, const sift_match* d_matches, float* src_xy, const float* d_src_xy,
+                      float* dst_xy, const float* d_dst_xy) {
+  const size_t ob = (size_t)(n_segments + 1) * sizeof(int);
+  HIP_TRY(c, hipMemcpyAsync(m_offsets, d_m_off, ob, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const size_t n = (size_t)(m_offsets[n_segments] < m_cap ? m_offsets[n_segments] : m_cap);
+  if (n) {
+    HIP_TRY(c, hipMemcpyAsync(matches, d_matches, n * sizeof(sift_match), hipMemcpyDeviceToHost, c->stream));
+    if (pairs) {
+      HIP_TRY(c, hipMemcpyAsync(src_xy, d_src_xy, n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(dst_xy, d_dst_xy, n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return SIFT_OK;
+}
+
+// The keypoints of both sides, for a stage that gathers point pairs.
+int upload_kpts(sift_ctx* c, sift_keypoint* d_q, const sift_keypoint* q_kpts, int q_cap, sift_keypoint* d_t,
+                const sift_keypoint* t_kpts, int t_cap) {
+  HIP_TRY(c, hipMemcpyAsync(d_q, q_kpts, (size_t)q_cap * sizeof(sift_keypoint), hipMemcpyHostToDevice, c->stream));
+  if (t_cap)
+    HIP_TRY(c, hipMemcpyAsync(d_t, t_kpts, (size_t)t_cap * sizeof(sift_keypoint), hipMemcpyHostToDevice, c->stream));
+  return SIFT_OK;
+}
 
 // The check_* functions hold the argument checks that the device and the host
 // form of an entry point share, in the order they fire; a call with nothing to
 // do (no queries, no segments) passes them whatever its buffers.
 
 // ---- BFMatcher(NORM_L1).knnMatch, src/main.cpp:25-27 ----
-int check_knn(sift_ctx* c, const float* query, int n_query, const float* train, int n_train, int k, const int* idx,
+int check_knn(sift_ctx* c, const void* query, int n_query, const void* train, int n_train, int k, const int* idx,
               const float* dist) {
   if (!c) return SIFT_E_INVALID;
   if (n_query < 0 || n_train < 0) return fail(c, SIFT_E_INVALID, "negative descriptor count");
@@ -65,7 +117,7 @@ int knn_device(sift_ctx* c, const float* q, int nq, const float* t, int nt, int 
 }
 
 // ---- a whole batch: segmented knnMatch, ratio test, point pairs (src/main.cpp:25-52) ----
-int check_seg(sift_ctx* c, const float* query, const int* q_offsets, int n_segments, int q_cap, const float* train,
+int check_seg(sift_ctx* c, const void* query, const int* q_offsets, int n_segments, int q_cap, const void* train,
               int t_cap, int k, const int* idx, const float* dist) {
   if (!c) return SIFT_E_INVALID;
   if (n_segments < 0 || q_cap < 0 || t_cap < 0) return fail(c, SIFT_E_INVALID, "negative count");
@@ -75,15 +127,110 @@ int check_seg(sift_ctx* c, const float* query, const int* q_offsets, int n_segme
   return SIFT_OK;
 }
 
-int knn_seg_device(sift_ctx* c, const float* q, const int* qoff, int n_segments, int q_cap, const float* t,
-                   const int* toff, int t_cap, int k, int splits, int* idx, float* dist, SegParts s) {
+// ---- the three segmented matchers: one metric description, one path ----
+// One segmented call: the buffers are device pointers.
+template <typename Row>
+struct SegCall {
+  const Row* q; const int* qoff; int n_segments, q_cap; const Row* t; const int* toff; int t_cap, k, splits;
+  int* idx; float* dist;
+};
+
+// A metric: scratch.hpp's row type and device pieces, and here the stage, the
+// split count and the launcher (match.hip, match_u8.hip, match_l2_u8.hip).
+struct MatchL1F32 : L1F32 {
+  static constexpr int kStage = ST_MATCH_SEG;
+  static constexpr auto splits = knn_seg_splits;
+  static void launch(hipStream_t st, const SegCall<Row>& A, const Seg& s) {
+    launch_knn_l1_seg(st, A.q, A.qoff, A.n_segments, A.q_cap, A.t, A.toff, A.t_cap, A.k, A.splits, s.tile_start,
+                      dev(s.parts.dist), dev(s.parts.idx), A.idx, A.dist);
+  }
+};
+struct MatchL1U8 : L1U8 {
+  static constexpr int kStage = ST_MATCH_U8;
+  static constexpr auto splits = knn_u8_seg_splits;
+  static void launch(hipStream_t st, const SegCall<Row>& A, const Seg& s) {
+    launch_knn_l1_u8_seg(st, A.q, A.qoff, A.n_segments, A.q_cap, A.t, A.toff, A.t_cap, A.k, A.splits, s.tile_start,
+                         dev(s.parts.dist), dev(s.parts.idx), A.idx, A.dist);
+  }
+};
+struct MatchL2SqrU8 : L2SqrU8 {
+  static constexpr int kStage = ST_MATCH_L2_U8;
+  static constexpr auto splits = knn_l2_u8_seg_splits;
+  static void launch(hipStream_t st, const SegCall<Row>& A, const Seg& s) {
+    launch_knn_l2sqr_u8_seg(st, A.q, A.qoff, A.n_segments, A.q_cap, A.t, A.toff, A.t_cap, A.k, A.splits, s.tile_start,
+                            s.q_norm, s.t_norm, dev(s.parts.dist), dev(s.parts.idx), A.idx, A.dist);
+  }
+};
+
+template <typename M>
+int knn_seg_device(sift_ctx* c, const SegCall<typename M::Row>& A, const typename M::Seg& s) {
   {
-    StageScope sc(c, ST_MATCH_SEG);  // the work depends on offsets only the device knows
-    launch_knn_l1_seg(c->stream, q, qoff, n_segments, q_cap, t, toff, t_cap, k, splits, s.tile_start,
-                      dev(s.parts.dist), dev(s.parts.idx), idx, dist);
+    StageScope sc(c, M::kStage);  // the work depends on offsets only the device knows
+    M::launch(c->stream, A, s);
   }
   HIP_TRY(c, hipGetLastError());
   return SIFT_OK;
+}
+
+// The _segmented_device entry points.
+template <typename M, typename Row = typename M::Row>
+int seg_match_device(sift_ctx* c, const Row* d_query, const int* d_q_offsets, int n_segments, int q_cap,
+                     const Row* d_train, const int* d_t_offsets, int t_cap, int k, int* d_idx, float* d_dist) {
+  int rc = check_seg(c, d_query, d_q_offsets, n_segments, q_cap, d_train, t_cap, k, d_idx, d_dist);
+  if (rc || n_segments == 0 || q_cap == 0) return rc;
+  if (!aligned16(d_query, d_train)) return fail(c, SIFT_E_INVALID, kRowsUnaligned);
+  (void)hipSetDevice(c->device);
+  const int splits = M::splits(q_cap, n_segments, t_cap, d_t_offsets != nullptr);
+  typename M::Seg S;
+  if ((rc = carve(c, &S, [&](Carver& a) { return M::layout(a, n_segments, q_cap, t_cap, splits); }))) return rc;
+  return knn_seg_device<M>(
+      c, {d_query, d_q_offsets, n_segments, q_cap, d_train, d_t_offsets, t_cap, k, splits, d_idx, d_dist}, S);
+}
+
+// The host forms after their checks: carve, upload, launch, the live rows come
+// back.  q_offsets null: one segment [0, q_cap) over the shared train set, whose
+// two offsets the library writes itself.
+template <typename M, typename Row = typename M::Row>
+int seg_host(sift_ctx* c, const Row* query, const int* q_offsets, int n_segments, int q_cap, const Row* train,
+             const int* t_offsets, int t_cap, int k, int* idx, float* dist) {
+  (void)hipSetDevice(c->device);
+  const int splits = M::splits(q_cap, n_segments, t_cap, t_offsets != nullptr);
+  SegHostOf<M> S;
+  int rc = carve(c, &S, [&](Carver& a) {
+    return seg_host_layout_of<M>(a, n_segments, q_cap, t_cap, t_offsets != nullptr, k, splits);
+  });
+  if (rc) return rc;
+  const size_t row = kDescLen * sizeof(Row), ob = (size_t)(n_segments + 1) * sizeof(int);
+  HIP_TRY(c, hipMemcpyAsync(S.query, query, q_cap * row, hipMemcpyHostToDevice, c->stream));
+  if (t_cap) HIP_TRY(c, hipMemcpyAsync(S.train, train, t_cap * row, hipMemcpyHostToDevice, c->stream));
+  if (q_offsets)
+    HIP_TRY(c, hipMemcpyAsync(S.q_off, q_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  else
+    launch_set_offsets(c->stream, S.q_off, 0, q_cap);
+  if (S.t_off) HIP_TRY(c, hipMemcpyAsync(S.t_off, t_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  if ((rc = knn_seg_device<M>(
+           c, {S.query, S.q_off, n_segments, q_cap, S.train, S.t_off, t_cap, k, splits, S.idx, S.dist}, S.seg)))
+    return rc;
+  const int whole[2] = {0, q_cap};
+  return copy_back_live_rows(c, q_offsets ? q_offsets : whole, n_segments, q_cap, k, idx, dist, S.idx, S.dist);
+}
+
+// The _segmented entry points.
+template <typename M, typename Row = typename M::Row>
+int seg_match_host(sift_ctx* c, const Row* query, const int* q_offsets, int n_segments, int q_cap, const Row* train,
+                   const int* t_offsets, int t_cap, int k, int* idx, float* dist) {
+  int rc = check_seg(c, query, q_offsets, n_segments, q_cap, train, t_cap, k, idx, dist);
+  if (rc || n_segments == 0 || q_cap == 0) return rc;
+  return seg_host<M>(c, query, q_offsets, n_segments, q_cap, train, t_offsets, t_cap, k, idx, dist);
+}
+
+// The one-segment byte entry points.
+template <typename M, typename Row = typename M::Row>
+int one_seg_match_host(sift_ctx* c, const Row* query, int n_query, const Row* train, int n_train, int k, int* idx,
+                       float* dist) {
+  int rc = check_knn(c, query, n_query, train, n_train, k, idx, dist);
+  if (rc || n_query == 0) return rc;
+  return seg_host<M>(c, query, nullptr, 1, n_query, train, nullptr, n_train, k, idx, dist);
 }
 
 // t_cap: the host form's train keypoint count (the device form never reads it: 0).
@@ -113,11 +260,7 @@ int ratio_device(sift_ctx* c, const int* idx, const float* dist, const int* qoff
   return SIFT_OK;
 }
 
-// ---- 8-bit descriptors: the quantiser and the segmented byte matcher (match_u8.hip) ----
-bool aligned16(const void* a, const void* b) {
-  return !((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15);
-}
-
+// ---- 8-bit descriptors: the quantiser (match_u8.hip) ----
 int check_quant(sift_ctx* c, const float* desc, int n, const uint8_t* out) {
   if (!c) return SIFT_E_INVALID;
   if (n < 0) return fail(c, SIFT_E_INVALID, "negative descriptor count");
@@ -135,44 +278,7 @@ int quant_device(sift_ctx* c, const float* desc, const int* n_rows, int row_cap,
   return SIFT_OK;
 }
 
-int check_seg_u8(sift_ctx* c, const uint8_t* query, const int* q_offsets, int n_segments, int q_cap,
-                 const uint8_t* train, int t_cap, int k, const int* idx, const float* dist) {
-  if (!c) return SIFT_E_INVALID;
-  if (n_segments < 0 || q_cap < 0 || t_cap < 0) return fail(c, SIFT_E_INVALID, "negative count");
-  if (k != 1 && k != 2) return fail(c, SIFT_E_INVALID, "k must be 1 or 2");
-  if (n_segments == 0 || q_cap == 0) return SIFT_OK;
-  if (!query || !q_offsets || !idx || !dist || (t_cap > 0 && !train)) return fail(c, SIFT_E_INVALID, "null buffer");
-  return SIFT_OK;
-}
-
-int knn_seg_u8_device(sift_ctx* c, const uint8_t* q, const int* qoff, int n_segments, int q_cap, const uint8_t* t,
-                      const int* toff, int t_cap, int k, int splits, int* idx, float* dist, SegPartsU8 s) {
-  {
-    StageScope sc(c, ST_MATCH_U8);  // the work depends on offsets only the device knows
-    launch_knn_l1_u8_seg(c->stream, q, qoff, n_segments, q_cap, t, toff, t_cap, k, splits, s.tile_start,
-                         dev(s.parts.dist), dev(s.parts.idx), idx, dist);
-  }
-  HIP_TRY(c, hipGetLastError());
-  return SIFT_OK;
-}
-
-// ---- squared L2 on the same byte rows (match_l2_u8.hip); the argument checks are check_seg_u8's ----
-int knn_seg_l2_u8_device(sift_ctx* c, const uint8_t* q, const int* qoff, int n_segments, int q_cap, const uint8_t* t,
-                         const int* toff, int t_cap, int k, int splits, int* idx, float* dist, SegPartsL2U8 s) {
-  {
-    StageScope sc(c, ST_MATCH_L2_U8);  // the work depends on offsets only the device knows
-    launch_knn_l2sqr_u8_seg(c->stream, q, qoff, n_segments, q_cap, t, toff, t_cap, k, splits, s.tile_start, s.q_norm,
-                            s.t_norm, dev(s.parts.dist), dev(s.parts.idx), idx, dist);
-  }
-  HIP_TRY(c, hipGetLastError());
-  return SIFT_OK;
-}
-
 // ---- spatially gated matching: the segmented matcher of a metric inside a search window (match_window.hip) ----
-bool known_metric(int metric) {
-  return metric == SIFT_METRIC_L1_F32 || metric == SIFT_METRIC_L1_U8 || metric == SIFT_METRIC_L2SQR_U8;
-}
-const char* const kBadMetric = "metric must be one of SIFT_METRIC_L1_F32, _L1_U8, _L2SQR_U8";
 size_t metric_row_bytes(int metric) { return metric == SIFT_METRIC_L1_F32 ? kDescLen * sizeof(float) : kDescLen; }
 
 int check_window(sift_ctx* c, int metric, const void* query, const sift_keypoint* q_kpts, const int* q_offsets,
@@ -190,14 +296,12 @@ int check_window(sift_ctx* c, int metric, const void* query, const sift_keypoint
   return SIFT_OK;
 }
 
-// A: everything but the grid and the scratch pieces.
-int window_device(sift_ctx* c, WindowArgs A, WindowGrid G, WindowParts P) {
-  A.nx = G.nx;
-  A.ny = G.ny;
-  A.inv_cell = G.inv_cell;
-  A.cell_end = P.cell_end;
-  A.cell_rows = P.cell_rows;
-  A.cell_xy = dev(P.cell_xy);
+// The caller's buffers (device pointers), the grid and the scratch pieces, as the kernels take them.
+int window_device(sift_ctx* c, int metric, const void* q, const sift_keypoint* q_kpts, const int* qoff, int n_segments,
+                  int q_cap, const void* t, const sift_keypoint* t_kpts, const int* toff, int t_cap, const double* H,
+                  const int* found, float radius, int k, int* idx, float* dist, WindowGrid G, WindowParts P) {
+  const WindowArgs A{metric, q, q_kpts, qoff, n_segments, q_cap, t, t_kpts, toff, t_cap, H, found, radius,
+                     G.nx, G.ny, G.inv_cell, P.cell_end, P.cell_rows, dev(P.cell_xy), k, idx, dist};
   {
     StageScope sc(c, ST_WINDOW_BIN, 0, 2.0 * (sizeof(sift_keypoint) + 12.0) * A.t_cap);
     HIP_TRY(c, launch_window_bin(c->stream, A));
@@ -257,42 +361,33 @@ int cross_device(sift_ctx* c, const int* idx, const float* dist, int fwd_k, cons
 }
 
 // The forward (k = fwd_k) and the reverse (k = 1, the sides exchanged) pass of
-// one metric into the tables of a CrossMatch layout.  A batch without train
-// rows has no reverse pass (and no neighbour to look up in its table).
+// one metric into the tables of its CrossMatch layout, carved here and handed
+// back in T.  A batch without train rows has no reverse pass (and no neighbour
+// to look up in its table).
 struct CrossArgs {
   const void *query, *train;
   const int *q_off, *t_off;
   int n_segments, q_cap, t_cap, fwd_k, fwd_splits, rev_splits;
 };
 
-int cross_passes(sift_ctx* c, const CrossArgs& A, const CrossMatch<SegParts>& S) {
-  const float *q = static_cast<const float*>(A.query), *t = static_cast<const float*>(A.train);
-  if (int rc = knn_seg_device(c, q, A.q_off, A.n_segments, A.q_cap, t, A.t_off, A.t_cap, A.fwd_k, A.fwd_splits,
-                              S.tab.idx, S.tab.dist, S.fwd))
+template <typename M>
+int cross_passes(sift_ctx* c, CrossArgs A, int blocks, CrossTables* T) {
+  using Row = typename M::Row;
+  const Row *q = static_cast<const Row*>(A.query), *t = static_cast<const Row*>(A.train);
+  A.fwd_splits = M::splits(A.q_cap, A.n_segments, A.t_cap, true);
+  A.rev_splits = M::splits(A.t_cap, A.n_segments, A.q_cap, true);
+  CrossMatch<typename M::Seg> S;
+  int rc = carve(c, &S, [&](Carver& a) {
+    return cross_match_layout_of<M>(a, A.n_segments, A.q_cap, A.t_cap, A.fwd_k, A.fwd_splits, A.rev_splits, blocks);
+  });
+  if (rc) return rc;
+  *T = S.tab;
+  if ((rc = knn_seg_device<M>(c, {q, A.q_off, A.n_segments, A.q_cap, t, A.t_off, A.t_cap, A.fwd_k, A.fwd_splits,
+                                  S.tab.idx, S.tab.dist}, S.fwd)))
     return rc;
   if (A.t_cap == 0) return SIFT_OK;
-  return knn_seg_device(c, t, A.t_off, A.n_segments, A.t_cap, q, A.q_off, A.q_cap, 1, A.rev_splits, S.tab.ridx,
-                        S.tab.rdist, S.rev);
-}
-
-int cross_passes(sift_ctx* c, const CrossArgs& A, const CrossMatch<SegPartsU8>& S) {
-  const uint8_t *q = static_cast<const uint8_t*>(A.query), *t = static_cast<const uint8_t*>(A.train);
-  if (int rc = knn_seg_u8_device(c, q, A.q_off, A.n_segments, A.q_cap, t, A.t_off, A.t_cap, A.fwd_k, A.fwd_splits,
-                                 S.tab.idx, S.tab.dist, S.fwd))
-    return rc;
-  if (A.t_cap == 0) return SIFT_OK;
-  return knn_seg_u8_device(c, t, A.t_off, A.n_segments, A.t_cap, q, A.q_off, A.q_cap, 1, A.rev_splits, S.tab.ridx,
-                           S.tab.rdist, S.rev);
-}
-
-int cross_passes(sift_ctx* c, const CrossArgs& A, const CrossMatch<SegPartsL2U8>& S) {
-  const uint8_t *q = static_cast<const uint8_t*>(A.query), *t = static_cast<const uint8_t*>(A.train);
-  if (int rc = knn_seg_l2_u8_device(c, q, A.q_off, A.n_segments, A.q_cap, t, A.t_off, A.t_cap, A.fwd_k, A.fwd_splits,
-                                    S.tab.idx, S.tab.dist, S.fwd))
-    return rc;
-  if (A.t_cap == 0) return SIFT_OK;
-  return knn_seg_l2_u8_device(c, t, A.t_off, A.n_segments, A.t_cap, q, A.q_off, A.q_cap, 1, A.rev_splits, S.tab.ridx,
-                              S.tab.rdist, S.rev);
+  return knn_seg_device<M>(
+      c, {t, A.t_off, A.n_segments, A.t_cap, q, A.q_off, A.q_cap, 1, A.rev_splits, S.tab.ridx, S.tab.rdist}, S.rev);
 }
 
 // ---- a whole batch: findHomography(RANSAC) per segment of the ratio stage's pairs (src/main.cpp:54-55) ----
@@ -335,7 +430,7 @@ int sift_knn_match_l1_device(sift_ctx* c, const float* d_query, int n_query, con
                              int k, int* d_idx, float* d_dist) {
   int rc = check_knn(c, d_query, n_query, d_train, n_train, k, d_idx, d_dist);
   if (rc || n_query == 0) return rc;
-  if (!rows_aligned(d_query, d_train)) return fail(c, SIFT_E_INVALID, kRowsUnaligned);
+  if (!aligned16(d_query, d_train)) return fail(c, SIFT_E_INVALID, kRowsUnaligned);
   (void)hipSetDevice(c->device);
   const int splits = knn_splits(n_query, n_train);
   KnnParts parts;
@@ -364,45 +459,13 @@ int sift_knn_match_l1(sift_ctx* c, const float* query, int n_query, const float*
 int sift_knn_match_l1_segmented_device(sift_ctx* c, const float* d_query, const int* d_q_offsets, int n_segments,
                                        int q_cap, const float* d_train, const int* d_t_offsets, int t_cap, int k,
                                        int* d_idx, float* d_dist) {
-  int rc = check_seg(c, d_query, d_q_offsets, n_segments, q_cap, d_train, t_cap, k, d_idx, d_dist);
-  if (rc || n_segments == 0 || q_cap == 0) return rc;
-  if (!rows_aligned(d_query, d_train)) return fail(c, SIFT_E_INVALID, kRowsUnaligned);
-  (void)hipSetDevice(c->device);
-  const int splits = knn_seg_splits(q_cap, n_segments, t_cap, d_t_offsets != nullptr);
-  SegParts S;
-  if ((rc = carve(c, &S, [&](Carver& a) { return seg_layout(a, n_segments, q_cap, splits); }))) return rc;
-  return knn_seg_device(c, d_query, d_q_offsets, n_segments, q_cap, d_train, d_t_offsets, t_cap, k, splits, d_idx,
-                        d_dist, S);
+  return seg_match_device<MatchL1F32>(c, d_query, d_q_offsets, n_segments, q_cap, d_train, d_t_offsets, t_cap, k, d_idx,
+                                      d_dist);
 }
 
 int sift_knn_match_l1_segmented(sift_ctx* c, const float* query, const int* q_offsets, int n_segments, int q_cap,
                                 const float* train, const int* t_offsets, int t_cap, int k, int* idx, float* dist) {
-  int rc = check_seg(c, query, q_offsets, n_segments, q_cap, train, t_cap, k, idx, dist);
-  if (rc || n_segments == 0 || q_cap == 0) return rc;
-  (void)hipSetDevice(c->device);
-  const int splits = knn_seg_splits(q_cap, n_segments, t_cap, t_offsets != nullptr);
-  SegHost S;
-  if ((rc = carve(c, &S, [&](Carver& a) {
-         return seg_host_layout(a, n_segments, q_cap, t_cap, t_offsets != nullptr, k, splits);
-       })))
-    return rc;
-  const size_t row = kDescLen * sizeof(float), ob = (size_t)(n_segments + 1) * sizeof(int);
-  HIP_TRY(c, hipMemcpyAsync(S.query, query, q_cap * row, hipMemcpyHostToDevice, c->stream));
-  if (t_cap) HIP_TRY(c, hipMemcpyAsync(S.train, train, t_cap * row, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(S.q_off, q_offsets, ob, hipMemcpyHostToDevice, c->stream));
-  if (S.t_off) HIP_TRY(c, hipMemcpyAsync(S.t_off, t_offsets, ob, hipMemcpyHostToDevice, c->stream));
-  if ((rc = knn_seg_device(c, S.query, S.q_off, n_segments, q_cap, S.train, S.t_off, t_cap, k, splits, S.idx, S.dist,
-                           S.seg)))
-    return rc;
-  // only the live rows come back: the others are left untouched, as in the device form
-  const int lo = clamp_off(q_offsets[0], q_cap), hi = clamp_off(q_offsets[n_segments], q_cap);
-  if (hi > lo) {
-    const size_t n = (size_t)(hi - lo) * k, o = (size_t)lo * k;
-    HIP_TRY(c, hipMemcpyAsync(idx + o, S.idx + o, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(dist + o, S.dist + o, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return SIFT_OK;
+  return seg_match_host<MatchL1F32>(c, query, q_offsets, n_segments, q_cap, train, t_offsets, t_cap, k, idx, dist);
 }
 
 int sift_descriptors_to_u8_device(sift_ctx* c, const float* d_desc, const int* d_n_rows, int row_cap,
@@ -430,147 +493,39 @@ int sift_descriptors_to_u8(sift_ctx* c, const float* desc, int n, uint8_t* out) 
 int sift_knn_match_l1_u8_segmented_device(sift_ctx* c, const uint8_t* d_query, const int* d_q_offsets,
                                           int n_segments, int q_cap, const uint8_t* d_train,
                                           const int* d_t_offsets, int t_cap, int k, int* d_idx, float* d_dist) {
-  int rc = check_seg_u8(c, d_query, d_q_offsets, n_segments, q_cap, d_train, t_cap, k, d_idx, d_dist);
-  if (rc || n_segments == 0 || q_cap == 0) return rc;
-  if (!aligned16(d_query, d_train)) return fail(c, SIFT_E_INVALID, kRowsUnaligned);
-  (void)hipSetDevice(c->device);
-  const int splits = knn_u8_seg_splits(q_cap, n_segments, t_cap, d_t_offsets != nullptr);
-  SegPartsU8 S;
-  if ((rc = carve(c, &S, [&](Carver& a) { return seg_u8_layout(a, n_segments, q_cap, splits); }))) return rc;
-  return knn_seg_u8_device(c, d_query, d_q_offsets, n_segments, q_cap, d_train, d_t_offsets, t_cap, k, splits,
-                           d_idx, d_dist, S);
+  return seg_match_device<MatchL1U8>(c, d_query, d_q_offsets, n_segments, q_cap, d_train, d_t_offsets, t_cap, k, d_idx,
+                                     d_dist);
 }
 
 int sift_knn_match_l1_u8_segmented(sift_ctx* c, const uint8_t* query, const int* q_offsets, int n_segments,
                                    int q_cap, const uint8_t* train, const int* t_offsets, int t_cap, int k,
                                    int* idx, float* dist) {
-  int rc = check_seg_u8(c, query, q_offsets, n_segments, q_cap, train, t_cap, k, idx, dist);
-  if (rc || n_segments == 0 || q_cap == 0) return rc;
-  (void)hipSetDevice(c->device);
-  const int splits = knn_u8_seg_splits(q_cap, n_segments, t_cap, t_offsets != nullptr);
-  SegHostU8 S;
-  if ((rc = carve(c, &S, [&](Carver& a) {
-         return seg_u8_host_layout(a, n_segments, q_cap, t_cap, t_offsets != nullptr, k, splits);
-       })))
-    return rc;
-  const size_t row = kDescLen, ob = (size_t)(n_segments + 1) * sizeof(int);
-  HIP_TRY(c, hipMemcpyAsync(S.query, query, q_cap * row, hipMemcpyHostToDevice, c->stream));
-  if (t_cap) HIP_TRY(c, hipMemcpyAsync(S.train, train, t_cap * row, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(S.q_off, q_offsets, ob, hipMemcpyHostToDevice, c->stream));
-  if (S.t_off) HIP_TRY(c, hipMemcpyAsync(S.t_off, t_offsets, ob, hipMemcpyHostToDevice, c->stream));
-  if ((rc = knn_seg_u8_device(c, S.query, S.q_off, n_segments, q_cap, S.train, S.t_off, t_cap, k, splits, S.idx,
-                              S.dist, S.seg)))
-    return rc;
-  // only the live rows come back: the others are left untouched, as in the device form
-  const int lo = clamp_off(q_offsets[0], q_cap), hi = clamp_off(q_offsets[n_segments], q_cap);
-  if (hi > lo) {
-    const size_t n = (size_t)(hi - lo) * k, o = (size_t)lo * k;
-    HIP_TRY(c, hipMemcpyAsync(idx + o, S.idx + o, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(dist + o, S.dist + o, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return SIFT_OK;
+  return seg_match_host<MatchL1U8>(c, query, q_offsets, n_segments, q_cap, train, t_offsets, t_cap, k, idx, dist);
 }
 
 // One segment [0, n_query) over the shared train set; the library writes the two offsets itself.
 int sift_knn_match_l1_u8(sift_ctx* c, const uint8_t* query, int n_query, const uint8_t* train, int n_train, int k,
                          int* idx, float* dist) {
-  if (!c) return SIFT_E_INVALID;
-  if (n_query < 0 || n_train < 0) return fail(c, SIFT_E_INVALID, "negative descriptor count");
-  if (k != 1 && k != 2) return fail(c, SIFT_E_INVALID, "k must be 1 or 2");
-  if (n_query == 0) return SIFT_OK;
-  if (!query || !idx || !dist || (n_train > 0 && !train)) return fail(c, SIFT_E_INVALID, "null buffer");
-  (void)hipSetDevice(c->device);
-  const int splits = knn_u8_seg_splits(n_query, 1, n_train, false);
-  SegHostU8 S;
-  int rc;
-  if ((rc = carve(c, &S, [&](Carver& a) { return seg_u8_host_layout(a, 1, n_query, n_train, false, k, splits); })))
-    return rc;
-  const size_t row = kDescLen;
-  HIP_TRY(c, hipMemcpyAsync(S.query, query, n_query * row, hipMemcpyHostToDevice, c->stream));
-  if (n_train) HIP_TRY(c, hipMemcpyAsync(S.train, train, n_train * row, hipMemcpyHostToDevice, c->stream));
-  launch_set_offsets(c->stream, S.q_off, 0, n_query);
-  if ((rc = knn_seg_u8_device(c, S.query, S.q_off, 1, n_query, S.train, nullptr, n_train, k, splits, S.idx, S.dist,
-                              S.seg)))
-    return rc;
-  HIP_TRY(c, hipMemcpyAsync(idx, S.idx, (size_t)n_query * k * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(dist, S.dist, (size_t)n_query * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return SIFT_OK;
+  return one_seg_match_host<MatchL1U8>(c, query, n_query, train, n_train, k, idx, dist);
 }
 
 int sift_knn_match_l2sqr_u8_segmented_device(sift_ctx* c, const uint8_t* d_query, const int* d_q_offsets,
                                              int n_segments, int q_cap, const uint8_t* d_train,
                                              const int* d_t_offsets, int t_cap, int k, int* d_idx, float* d_dist) {
-  int rc = check_seg_u8(c, d_query, d_q_offsets, n_segments, q_cap, d_train, t_cap, k, d_idx, d_dist);
-  if (rc || n_segments == 0 || q_cap == 0) return rc;
-  if (!aligned16(d_query, d_train)) return fail(c, SIFT_E_INVALID, kRowsUnaligned);
-  (void)hipSetDevice(c->device);
-  const int splits = knn_l2_u8_seg_splits(q_cap, n_segments, t_cap, d_t_offsets != nullptr);
-  SegPartsL2U8 S;
-  if ((rc = carve(c, &S, [&](Carver& a) { return seg_l2_u8_layout(a, n_segments, q_cap, t_cap, splits); })))
-    return rc;
-  return knn_seg_l2_u8_device(c, d_query, d_q_offsets, n_segments, q_cap, d_train, d_t_offsets, t_cap, k, splits,
-                              d_idx, d_dist, S);
+  return seg_match_device<MatchL2SqrU8>(c, d_query, d_q_offsets, n_segments, q_cap, d_train, d_t_offsets, t_cap, k,
+                                        d_idx, d_dist);
 }
 
 int sift_knn_match_l2sqr_u8_segmented(sift_ctx* c, const uint8_t* query, const int* q_offsets, int n_segments,
                                       int q_cap, const uint8_t* train, const int* t_offsets, int t_cap, int k,
                                       int* idx, float* dist) {
-  int rc = check_seg_u8(c, query, q_offsets, n_segments, q_cap, train, t_cap, k, idx, dist);
-  if (rc || n_segments == 0 || q_cap == 0) return rc;
-  (void)hipSetDevice(c->device);
-  const int splits = knn_l2_u8_seg_splits(q_cap, n_segments, t_cap, t_offsets != nullptr);
-  SegHostL2U8 S;
-  if ((rc = carve(c, &S, [&](Carver& a) {
-         return seg_l2_u8_host_layout(a, n_segments, q_cap, t_cap, t_offsets != nullptr, k, splits);
-       })))
-    return rc;
-  const size_t row = kDescLen, ob = (size_t)(n_segments + 1) * sizeof(int);
-  HIP_TRY(c, hipMemcpyAsync(S.query, query, q_cap * row, hipMemcpyHostToDevice, c->stream));
-  if (t_cap) HIP_TRY(c, hipMemcpyAsync(S.train, train, t_cap * row, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(S.q_off, q_offsets, ob, hipMemcpyHostToDevice, c->stream));
-  if (S.t_off) HIP_TRY(c, hipMemcpyAsync(S.t_off, t_offsets, ob, hipMemcpyHostToDevice, c->stream));
-  if ((rc = knn_seg_l2_u8_device(c, S.query, S.q_off, n_segments, q_cap, S.train, S.t_off, t_cap, k, splits, S.idx,
-                                 S.dist, S.seg)))
-    return rc;
-  // only the live rows come back: the others are left untouched, as in the device form
-  const int lo = clamp_off(q_offsets[0], q_cap), hi = clamp_off(q_offsets[n_segments], q_cap);
-  if (hi > lo) {
-    const size_t n = (size_t)(hi - lo) * k, o = (size_t)lo * k;
-    HIP_TRY(c, hipMemcpyAsync(idx + o, S.idx + o, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(dist + o, S.dist + o, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return SIFT_OK;
+  return seg_match_host<MatchL2SqrU8>(c, query, q_offsets, n_segments, q_cap, train, t_offsets, t_cap, k, idx, dist);
 }
 
 // One segment [0, n_query) over the shared train set; the library writes the two offsets itself.
 int sift_knn_match_l2sqr_u8(sift_ctx* c, const uint8_t* query, int n_query, const uint8_t* train, int n_train, int k,
                             int* idx, float* dist) {
-  if (!c) return SIFT_E_INVALID;
-  if (n_query < 0 || n_train < 0) return fail(c, SIFT_E_INVALID, "negative descriptor count");
-  if (k != 1 && k != 2) return fail(c, SIFT_E_INVALID, "k must be 1 or 2");
-  if (n_query == 0) return SIFT_OK;
-  if (!query || !idx || !dist || (n_train > 0 && !train)) return fail(c, SIFT_E_INVALID, "null buffer");
-  (void)hipSetDevice(c->device);
-  const int splits = knn_l2_u8_seg_splits(n_query, 1, n_train, false);
-  SegHostL2U8 S;
-  int rc;
-  if ((rc = carve(c, &S,
-                  [&](Carver& a) { return seg_l2_u8_host_layout(a, 1, n_query, n_train, false, k, splits); })))
-    return rc;
-  const size_t row = kDescLen;
-  HIP_TRY(c, hipMemcpyAsync(S.query, query, n_query * row, hipMemcpyHostToDevice, c->stream));
-  if (n_train) HIP_TRY(c, hipMemcpyAsync(S.train, train, n_train * row, hipMemcpyHostToDevice, c->stream));
-  launch_set_offsets(c->stream, S.q_off, 0, n_query);
-  if ((rc = knn_seg_l2_u8_device(c, S.query, S.q_off, 1, n_query, S.train, nullptr, n_train, k, splits, S.idx,
-                                 S.dist, S.seg)))
-    return rc;
-  HIP_TRY(c, hipMemcpyAsync(idx, S.idx, (size_t)n_query * k * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(dist, S.dist, (size_t)n_query * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return SIFT_OK;
+  return one_seg_match_host<MatchL2SqrU8>(c, query, n_query, train, n_train, k, idx, dist);
 }
 
 int sift_ratio_matches_device(sift_ctx* c, const int* d_idx, const float* d_dist, const int* d_q_offsets,
@@ -606,29 +561,12 @@ int sift_ratio_matches(sift_ctx* c, const int* idx, const float* dist, const int
   HIP_TRY(c, hipMemcpyAsync(S.dist, dist, (size_t)q_cap * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(S.q_off, q_offsets, ob, hipMemcpyHostToDevice, c->stream));
   if (S.t_off) HIP_TRY(c, hipMemcpyAsync(S.t_off, t_offsets, ob, hipMemcpyHostToDevice, c->stream));
-  if (q_kpts) {
-    HIP_TRY(c, hipMemcpyAsync(S.q_kpts, q_kpts, (size_t)q_cap * sizeof(sift_keypoint), hipMemcpyHostToDevice,
-                              c->stream));
-    if (t_cap)
-      HIP_TRY(c, hipMemcpyAsync(S.t_kpts, t_kpts, (size_t)t_cap * sizeof(sift_keypoint), hipMemcpyHostToDevice,
-                                c->stream));
-  }
+  if (q_kpts && (rc = upload_kpts(c, S.q_kpts, q_kpts, q_cap, S.t_kpts, t_kpts, t_cap))) return rc;
   if ((rc = ratio_device(c, S.idx, S.dist, S.q_off, n_segments, q_cap, ratio, S.q_kpts, S.t_kpts, S.t_off, S.matches,
                          S.src_xy, S.dst_xy, m_cap, S.m_off, S.blk_scan)))
     return rc;
-  HIP_TRY(c, hipMemcpyAsync(m_offsets, S.m_off, ob, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  // only the written records come back
-  const size_t n = (size_t)(m_offsets[n_segments] < m_cap ? m_offsets[n_segments] : m_cap);
-  if (n) {
-    HIP_TRY(c, hipMemcpyAsync(matches, S.matches, n * sizeof(sift_match), hipMemcpyDeviceToHost, c->stream));
-    if (q_kpts) {
-      HIP_TRY(c, hipMemcpyAsync(src_xy, S.src_xy, n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(dst_xy, S.dst_xy, n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  return SIFT_OK;
+  return copy_back_records(c, n_segments, m_cap, q_kpts != nullptr, m_offsets, S.m_off, matches, S.matches, src_xy,
+                           S.src_xy, dst_xy, S.dst_xy);
 }
 
 int sift_cross_check_matches_device(sift_ctx* c, const int* d_idx, const float* d_dist, int fwd_k,
@@ -667,29 +605,12 @@ int sift_cross_check_matches(sift_ctx* c, const int* idx, const float* dist, int
     HIP_TRY(c, hipMemcpyAsync(S.ridx, ridx, (size_t)t_cap * rev_k * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(S.q_off, q_offsets, ob, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(S.t_off, t_offsets, ob, hipMemcpyHostToDevice, c->stream));
-  if (q_kpts) {
-    HIP_TRY(c, hipMemcpyAsync(S.q_kpts, q_kpts, (size_t)q_cap * sizeof(sift_keypoint), hipMemcpyHostToDevice,
-                              c->stream));
-    if (t_cap)
-      HIP_TRY(c, hipMemcpyAsync(S.t_kpts, t_kpts, (size_t)t_cap * sizeof(sift_keypoint), hipMemcpyHostToDevice,
-                                c->stream));
-  }
+  if (q_kpts && (rc = upload_kpts(c, S.q_kpts, q_kpts, q_cap, S.t_kpts, t_kpts, t_cap))) return rc;
   if ((rc = cross_device(c, S.idx, S.dist, fwd_k, S.q_off, n_segments, q_cap, S.ridx, rev_k, S.t_off, t_cap, ratio,
                          S.q_kpts, S.t_kpts, S.matches, S.src_xy, S.dst_xy, m_cap, S.m_off, S.blk_scan)))
     return rc;
-  HIP_TRY(c, hipMemcpyAsync(m_offsets, S.m_off, ob, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  // only the written records come back
-  const size_t n = (size_t)(m_offsets[n_segments] < m_cap ? m_offsets[n_segments] : m_cap);
-  if (n) {
-    HIP_TRY(c, hipMemcpyAsync(matches, S.matches, n * sizeof(sift_match), hipMemcpyDeviceToHost, c->stream));
-    if (q_kpts) {
-      HIP_TRY(c, hipMemcpyAsync(src_xy, S.src_xy, n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(dst_xy, S.dst_xy, n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  return SIFT_OK;
+  return copy_back_records(c, n_segments, m_cap, q_kpts != nullptr, m_offsets, S.m_off, matches, S.matches, src_xy,
+                           S.src_xy, dst_xy, S.dst_xy);
 }
 
 int sift_cross_match_segmented_device(sift_ctx* c, int metric, const void* d_query, const int* d_q_offsets,
@@ -698,8 +619,7 @@ int sift_cross_match_segmented_device(sift_ctx* c, int metric, const void* d_que
                                       const sift_keypoint* d_t_kpts, sift_match* d_matches, float* d_src_xy,
                                       float* d_dst_xy, int m_cap, int* d_m_offsets) {
   if (!c) return SIFT_E_INVALID;
-  if (metric != SIFT_METRIC_L1_F32 && metric != SIFT_METRIC_L1_U8 && metric != SIFT_METRIC_L2SQR_U8)
-    return fail(c, SIFT_E_INVALID, "metric must be one of SIFT_METRIC_L1_F32, _L1_U8, _L2SQR_U8");
+  if (!known_metric(metric)) return fail(c, SIFT_E_INVALID, kBadMetric);
   if (n_segments < 0 || q_cap < 0 || t_cap < 0 || m_cap < 0) return fail(c, SIFT_E_INVALID, "negative count");
   const int fwd_k = ratio > 0 ? 2 : 1;
   int rc = check_cross_ratio(c, ratio, fwd_k);
@@ -711,40 +631,13 @@ int sift_cross_match_segmented_device(sift_ctx* c, int metric, const void* d_que
   (void)hipSetDevice(c->device);
   // Every piece of both passes and of the stage is carved before the first
   // enqueue: the block cannot grow (and move the tables) between the launches.
-  CrossArgs A{d_query, d_train, d_q_offsets, d_t_offsets, n_segments, q_cap, t_cap, fwd_k, 1, 1};
+  const CrossArgs A{d_query, d_train, d_q_offsets, d_t_offsets, n_segments, q_cap, t_cap, fwd_k, 1, 1};
   const int blocks = cross_blocks(q_cap);
   CrossTables T;
-  if (metric == SIFT_METRIC_L1_F32) {
-    A.fwd_splits = knn_seg_splits(q_cap, n_segments, t_cap, true);
-    A.rev_splits = knn_seg_splits(t_cap, n_segments, q_cap, true);
-    CrossMatch<SegParts> S;
-    if ((rc = carve(c, &S, [&](Carver& a) {
-           return cross_match_layout(a, n_segments, q_cap, t_cap, fwd_k, A.fwd_splits, A.rev_splits, blocks);
-         })) ||
-        (rc = cross_passes(c, A, S)))
-      return rc;
-    T = S.tab;
-  } else if (metric == SIFT_METRIC_L1_U8) {
-    A.fwd_splits = knn_u8_seg_splits(q_cap, n_segments, t_cap, true);
-    A.rev_splits = knn_u8_seg_splits(t_cap, n_segments, q_cap, true);
-    CrossMatch<SegPartsU8> S;
-    if ((rc = carve(c, &S, [&](Carver& a) {
-           return cross_match_u8_layout(a, n_segments, q_cap, t_cap, fwd_k, A.fwd_splits, A.rev_splits, blocks);
-         })) ||
-        (rc = cross_passes(c, A, S)))
-      return rc;
-    T = S.tab;
-  } else {
-    A.fwd_splits = knn_l2_u8_seg_splits(q_cap, n_segments, t_cap, true);
-    A.rev_splits = knn_l2_u8_seg_splits(t_cap, n_segments, q_cap, true);
-    CrossMatch<SegPartsL2U8> S;
-    if ((rc = carve(c, &S, [&](Carver& a) {
-           return cross_match_l2_u8_layout(a, n_segments, q_cap, t_cap, fwd_k, A.fwd_splits, A.rev_splits, blocks);
-         })) ||
-        (rc = cross_passes(c, A, S)))
-      return rc;
-    T = S.tab;
-  }
+  rc = metric == SIFT_METRIC_L1_F32  ? cross_passes<MatchL1F32>(c, A, blocks, &T)
+       : metric == SIFT_METRIC_L1_U8 ? cross_passes<MatchL1U8>(c, A, blocks, &T)
+                                     : cross_passes<MatchL2SqrU8>(c, A, blocks, &T);
+  if (rc) return rc;
   return cross_device(c, T.idx, T.dist, fwd_k, d_q_offsets, n_segments, q_cap, T.ridx, 1, d_t_offsets, t_cap, ratio,
                       d_q_kpts, d_t_kpts, d_matches, d_src_xy, d_dst_xy, m_cap, d_m_offsets, T.blk_scan);
 }
@@ -763,24 +656,8 @@ int sift_knn_match_window_segmented_device(sift_ctx* c, int metric, const void* 
   const WindowGrid G = window_grid(radius, rows, cols, t_cap, n_grids);
   WindowParts P;
   if ((rc = carve(c, &P, [&](Carver& a) { return window_layout(a, n_grids, G.nx * G.ny, t_cap); }))) return rc;
-  WindowArgs A{};
-  A.metric = metric;
-  A.q = d_query;
-  A.q_kpts = d_q_kpts;
-  A.qoff = d_q_offsets;
-  A.nseg = n_segments;
-  A.q_cap = q_cap;
-  A.t = d_train;
-  A.t_kpts = d_t_kpts;
-  A.toff = d_t_offsets;
-  A.t_cap = t_cap;
-  A.H = d_H;
-  A.found = d_found;
-  A.radius = radius;
-  A.k = k;
-  A.idx = d_idx;
-  A.dist = d_dist;
-  return window_device(c, A, G, P);
+  return window_device(c, metric, d_query, d_q_kpts, d_q_offsets, n_segments, q_cap, d_train, d_t_kpts, d_t_offsets,
+                       t_cap, d_H, d_found, radius, k, d_idx, d_dist, G, P);
 }
 
 int sift_knn_match_window_segmented(sift_ctx* c, int metric, const void* query, const sift_keypoint* q_kpts,
@@ -816,33 +693,10 @@ int sift_knn_match_window_segmented(sift_ctx* c, int metric, const void* query, 
     HIP_TRY(c, hipMemcpyAsync(S.H, H, (size_t)n_segments * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
   if (S.found)
     HIP_TRY(c, hipMemcpyAsync(S.found, found, (size_t)n_segments * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  WindowArgs A{};
-  A.metric = metric;
-  A.q = S.query;
-  A.q_kpts = S.q_kpts;
-  A.qoff = S.q_off;
-  A.nseg = n_segments;
-  A.q_cap = q_cap;
-  A.t = S.train;
-  A.t_kpts = S.t_kpts;
-  A.toff = S.t_off;
-  A.t_cap = t_cap;
-  A.H = S.H;
-  A.found = S.found;
-  A.radius = radius;
-  A.k = k;
-  A.idx = S.idx;
-  A.dist = S.dist;
-  if ((rc = window_device(c, A, G, S.win))) return rc;
-  // only the live rows come back: the others are left untouched, as in the device form
-  const int lo = clamp_off(q_offsets[0], q_cap), hi = clamp_off(q_offsets[n_segments], q_cap);
-  if (hi > lo) {
-    const size_t n = (size_t)(hi - lo) * k, o = (size_t)lo * k;
-    HIP_TRY(c, hipMemcpyAsync(idx + o, S.idx + o, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(dist + o, S.dist + o, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return SIFT_OK;
+  if ((rc = window_device(c, metric, S.query, S.q_kpts, S.q_off, n_segments, q_cap, S.train, S.t_kpts, S.t_off, t_cap,
+                          S.H, S.found, radius, k, S.idx, S.dist, G, S.win)))
+    return rc;
+  return copy_back_live_rows(c, q_offsets, n_segments, q_cap, k, idx, dist, S.idx, S.dist);
 }
 
 int sift_bgr8_to_gray_device(sift_ctx* c, const uint8_t* d_bgr, int batch, int rows, int cols, size_t row_stride,

@@ -40,27 +40,7 @@ constexpr int kQT = 64;  // queries per workgroup
 constexpr int kTC = 64;  // train rows per LDS chunk
 constexpr int kV4 = kDescLen / 4;
 
-struct Best2 {
-  float d1, d2;
-  int i1, i2;
-};
-
-// (d, i) < (e, j) lexicographically; i = -1 (empty slot) sorts last via d = +inf.
-// No index is below -1, so a candidate at d = +inf never displaces an empty
-// slot: such a row is never a neighbour (sift_hip.h).
-__device__ __forceinline__ bool lex_lt(float d, int i, float e, int j) { return d < e || (d == e && i < j); }
-
-__device__ __forceinline__ void insert(Best2& b, float d, int i) {
-  if (lex_lt(d, i, b.d1, b.i1)) {
-    b.d2 = b.d1;
-    b.i2 = b.i1;
-    b.d1 = d;
-    b.i1 = i;
-  } else if (lex_lt(d, i, b.d2, b.i2)) {
-    b.d2 = d;
-    b.i2 = i;
-  }
-}
+using Best2 = Top2<float>;  // match_seg.hpp: the list, its order and insert()
 
 // normL1_ of one query (registers) against one staged train row (LDS, the same
 // row for every lane): the summation order of the file comment.
@@ -99,7 +79,7 @@ __global__ __launch_bounds__(256) void knn_l1_kernel(const float* __restrict__ q
 #pragma unroll
     for (int v = 0; v < kV4; ++v) qv[v] = qp[v];
   }
-  Best2 best{INFINITY, INFINITY, -1, -1};
+  Best2 best = top2_empty<float>();
   const int t0 = blockIdx.y * per_split, t1 = min(nt, t0 + per_split);
   for (int c0 = t0; c0 < t1; c0 += kTC) {
     const int nrow = min(kTC, t1 - c0);
@@ -133,25 +113,21 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const float2* __restrict
                                                         int* __restrict__ idx, float* __restrict__ dist) {
   const int qi = blockIdx.x * 256 + threadIdx.x;
   if (qi >= nq) return;
-  Best2 best{INFINITY, INFINITY, -1, -1};
+  Best2 best = top2_empty<float>();
   for (int s = 0; s < splits; ++s) {
     const float2 d = part_d[(long long)s * nq + qi];
     const int2 i = part_i[(long long)s * nq + qi];
     insert(best, d.x, i.x);
     insert(best, d.y, i.y);
   }
-  idx[(long long)qi * k] = best.i1;
-  dist[(long long)qi * k] = best.d1;
-  if (k == 2) {
-    idx[(long long)qi * k + 1] = best.i2;
-    dist[(long long)qi * k + 1] = best.d2;
-  }
+  write_knn(best, qi, k, idx, dist);
 }
 
 // ---- segmented form: a whole batch in one launch sequence ---------------------
-// The clamped offsets (clamp_row), the segment search (seg_of) and the query-tile
-// table (seg_tiles_kernel, here with 64-query tiles) are match_seg.hpp's, shared
-// with the byte matcher.
+// The clamped offsets (clamp_row), the segment search (seg_of), the query-tile
+// table (seg_tiles_kernel, here with 64-query tiles) and the merge of the
+// splits' lists (knn_seg_merge_kernel) are match_seg.hpp's, shared with the
+// byte matchers.
 
 // knn_l1_kernel's tile (64 queries in VGPRs, 64-row train chunks in LDS,
 // broadcast reads) with the bounds taken from the device: grid.x covers the
@@ -173,7 +149,7 @@ __global__ __launch_bounds__(256) void knn_l1_seg_kernel(const float* __restrict
   const int b = seg_of(tile_start, nseg, 0x7fffffff, tile);
   const int qe = clamp_row(qoff[b + 1], q_cap);
   const int qi = clamp_row(qoff[b], q_cap) + (tile - tile_start[b]) * kQT + lane;  // < qe for lane 0
-  int ts = 0, te = t_cap;
+  int ts = 0, te = t_cap;  // train_range() of match_seg.hpp, restated (profiles/match_refactor_isa.txt)
   if (toff) {
     ts = clamp_row(toff[b], t_cap);
     te = clamp_row(toff[b + 1], t_cap);
@@ -188,7 +164,7 @@ __global__ __launch_bounds__(256) void knn_l1_seg_kernel(const float* __restrict
 #pragma unroll
     for (int v = 0; v < kV4; ++v) qv[v] = qp[v];
   }
-  Best2 best{INFINITY, INFINITY, -1, -1};
+  Best2 best = top2_empty<float>();
   for (int c0 = t0; c0 < t1; c0 += kTC) {
     const int nrow = min(kTC, t1 - c0);
     __syncthreads();
@@ -209,40 +185,12 @@ __global__ __launch_bounds__(256) void knn_l1_seg_kernel(const float* __restrict
       insert(best, md[w][1][lane], mi[w][1][lane]);
     }
     if (splits == 1) {
-      idx[(long long)qi * k] = best.i1;
-      dist[(long long)qi * k] = best.d1;
-      if (k == 2) {
-        idx[(long long)qi * k + 1] = best.i2;
-        dist[(long long)qi * k + 1] = best.d2;
-      }
+      write_knn(best, qi, k, idx, dist);
     } else {
       const long long o = (long long)blockIdx.y * q_cap + qi;
       part_d[o] = make_float2(best.d1, best.d2);
       part_i[o] = make_int2(best.i1, best.i2);
     }
-  }
-}
-
-// knn_merge_kernel over the live rows [clamp(qoff[0]), clamp(qoff[nseg])) only.
-__global__ __launch_bounds__(256) void knn_seg_merge_kernel(const float2* __restrict__ part_d,
-                                                            const int2* __restrict__ part_i,
-                                                            const int* __restrict__ qoff, int nseg, int q_cap,
-                                                            int splits, int k, int* __restrict__ idx,
-                                                            float* __restrict__ dist) {
-  const int qi = blockIdx.x * 256 + threadIdx.x;
-  if (qi < clamp_row(qoff[0], q_cap) || qi >= clamp_row(qoff[nseg], q_cap)) return;
-  Best2 best{INFINITY, INFINITY, -1, -1};
-  for (int s = 0; s < splits; ++s) {
-    const float2 d = part_d[(long long)s * q_cap + qi];
-    const int2 i = part_i[(long long)s * q_cap + qi];
-    insert(best, d.x, i.x);
-    insert(best, d.y, i.y);
-  }
-  idx[(long long)qi * k] = best.i1;
-  dist[(long long)qi * k] = best.d1;
-  if (k == 2) {
-    idx[(long long)qi * k + 1] = best.i2;
-    dist[(long long)qi * k + 1] = best.d2;
   }
 }
 
@@ -378,7 +326,7 @@ void launch_knn_l1_seg(hipStream_t st, const float* q, const int* qoff, int n_se
   hipLaunchKernelGGL(knn_l1_seg_kernel, grid, dim3(256), 0, st, q, qoff, n_segments, q_cap, t, toff, t_cap,
                      tile_start, splits, k, part_d, part_i, idx, dist);
   if (splits > 1)
-    hipLaunchKernelGGL(knn_seg_merge_kernel, dim3((q_cap + 255) / 256), dim3(256), 0, st, part_d, part_i, qoff,
+    hipLaunchKernelGGL(knn_seg_merge_kernel<float2>, dim3((q_cap + 255) / 256), dim3(256), 0, st, part_d, part_i, qoff,
                        n_segments, q_cap, splits, k, idx, dist);
 }
 

@@ -55,7 +55,6 @@ constexpr int kNormPad = kL2NormPad;     // t_norm entries past t_cap a tail til
 static_assert(kNormPad >= kTR, "a tail tile reads the norms of a whole tile");
 constexpr unsigned kBias = 0x80808080u;
 constexpr unsigned kEmptyKey = 0xffffffffu;  // above (8,323,200 << 9) | 511
-constexpr int kEmptyDist = 0x7fffffff;       // decoded form of an empty slot (index -1)
 
 // ---- norms ---------------------------------------------------------------------
 __device__ __forceinline__ int sq4(unsigned w) {
@@ -88,37 +87,10 @@ __global__ __launch_bounds__(256) void l2_norms_kernel(const uint4* __restrict__
 }
 
 // ---- matcher -------------------------------------------------------------------
-struct BestI {  // decoded top-2: distances ascending, (kEmptyDist, -1) for an empty slot
-  int d1, d2, i1, i2;
-};
-
-// (d, i) < (e, j) lexicographically; an empty slot sorts last via its distance.
-__device__ __forceinline__ bool lex_lt(int d, int i, int e, int j) { return d < e || (d == e && i < j); }
-
-__device__ __forceinline__ void insert(BestI& b, int d, int i) {
-  if (lex_lt(d, i, b.d1, b.i1)) {
-    b.d2 = b.d1;
-    b.i2 = b.i1;
-    b.d1 = d;
-    b.i1 = i;
-  } else if (lex_lt(d, i, b.d2, b.i2)) {
-    b.d2 = d;
-    b.i2 = i;
-  }
-}
+using BestI = Top2<int>;  // match_seg.hpp: the decoded list, its order, insert() and write_knn()
 
 __device__ __forceinline__ void fold(BestI& b, unsigned key, int base) {
   if (key != kEmptyKey) insert(b, (int)(key >> kLocBits), (int)(key & (kChunk - 1)) + base);
-}
-
-__device__ __forceinline__ void write_knn(const BestI& b, long long qi, int k, int* __restrict__ idx,
-                                          float* __restrict__ dist) {
-  idx[qi * k] = b.i1;
-  dist[qi * k] = b.i1 < 0 ? INFINITY : (float)b.d1;
-  if (k == 2) {
-    idx[qi * k + 1] = b.i2;
-    dist[qi * k + 1] = b.i2 < 0 ? INFINITY : (float)b.d2;
-  }
 }
 
 struct L2Args {
@@ -207,7 +179,7 @@ __global__ __launch_bounds__(256) void knn_l2sqr_u8_seg_kernel(L2Args A) {
   const int b = seg_of(A.tile_start, A.nseg, 0x7fffffff, tile);
   const int qe = clamp_row(A.qoff[b + 1], A.q_cap);
   const int q0 = clamp_row(A.qoff[b], A.q_cap) + (tile - A.tile_start[b]) * kL2Tile + col;  // < qe for lane 0
-  int ts = 0, te = A.t_cap;
+  int ts = 0, te = A.t_cap;  // train_range() of match_seg.hpp, restated (profiles/match_refactor_isa.txt)
   if (A.toff) {
     ts = clamp_row(A.toff[b], A.t_cap);
     te = clamp_row(A.toff[b + 1], A.t_cap);
@@ -232,7 +204,7 @@ __global__ __launch_bounds__(256) void knn_l2sqr_u8_seg_kernel(L2Args A) {
   }
   BestI best[kQB];
 #pragma unroll
-  for (int s = 0; s < kQB; ++s) best[s] = BestI{kEmptyDist, kEmptyDist, -1, -1};
+  for (int s = 0; s < kQB; ++s) best[s] = top2_empty<int>();
 
   if (w0 < w1) {
     unsigned k1[kQB], k2[kQB];
@@ -299,24 +271,6 @@ __global__ __launch_bounds__(256) void knn_l2sqr_u8_seg_kernel(L2Args A) {
   }
 }
 
-// The splits' lists of the live rows [clamp(qoff[0]), clamp(qoff[nseg])) only.
-__global__ __launch_bounds__(256) void knn_l2sqr_u8_merge_kernel(const int2* __restrict__ part_d,
-                                                                 const int2* __restrict__ part_i,
-                                                                 const int* __restrict__ qoff, int nseg, int q_cap,
-                                                                 int splits, int k, int* __restrict__ idx,
-                                                                 float* __restrict__ dist) {
-  const int qi = blockIdx.x * 256 + threadIdx.x;
-  if (qi < clamp_row(qoff[0], q_cap) || qi >= clamp_row(qoff[nseg], q_cap)) return;
-  BestI best{kEmptyDist, kEmptyDist, -1, -1};
-  for (int s = 0; s < splits; ++s) {
-    const int2 d = part_d[(long long)s * q_cap + qi];
-    const int2 i = part_i[(long long)s * q_cap + qi];
-    insert(best, d.x, i.x);
-    insert(best, d.y, i.y);
-  }
-  write_knn(best, qi, k, idx, dist);
-}
-
 }  // namespace
 
 int knn_l2_u8_seg_max_tiles(int q_cap, int n_segments) { return q_cap / kL2Tile + n_segments; }
@@ -345,7 +299,7 @@ void launch_knn_l2sqr_u8_seg(hipStream_t st, const uint8_t* q, const int* qoff, 
   dim3 grid(knn_l2_u8_seg_max_tiles(q_cap, n_segments), splits);
   hipLaunchKernelGGL(knn_l2sqr_u8_seg_kernel, grid, dim3(256), 0, st, A);
   if (splits > 1)
-    hipLaunchKernelGGL(knn_l2sqr_u8_merge_kernel, dim3((q_cap + 255) / 256), dim3(256), 0, st, part_d, part_i, qoff,
+    hipLaunchKernelGGL(knn_seg_merge_kernel<int2>, dim3((q_cap + 255) / 256), dim3(256), 0, st, part_d, part_i, qoff,
                        n_segments, q_cap, splits, k, idx, dist);
 }
 

@@ -61,26 +61,7 @@ constexpr int kWinQueries = kWinBlock / kWinGroup;  // queries per workgroup
 constexpr float kWinSlack = 1.f / 4194304.f;      // 2^-22, see the file comment
 static_assert(kDescLen == 16 * kWinGroup, "lane k owns elements 8g + k (floats) or bytes [16k, 16k + 16)");
 
-struct Best2 {
-  float d1, d2;
-  int i1, i2;
-};
-
-// match.hip's order: (d, i) < (e, j) lexicographically; an empty slot is
-// (+inf, -1), which no candidate at d = +inf displaces.
-__device__ __forceinline__ bool lex_lt(float d, int i, float e, int j) { return d < e || (d == e && i < j); }
-
-__device__ __forceinline__ void insert(Best2& b, float d, int i) {
-  if (lex_lt(d, i, b.d1, b.i1)) {
-    b.d2 = b.d1;
-    b.i2 = b.i1;
-    b.d1 = d;
-    b.i1 = i;
-  } else if (lex_lt(d, i, b.d2, b.i2)) {
-    b.d2 = d;
-    b.i2 = i;
-  }
-}
+using Best2 = Top2<float>;  // match_seg.hpp: every metric's distance is a float here, in the dense matchers' order
 
 // Monotone non-decreasing in v; NaN gives 0.
 __device__ __forceinline__ int cell_of(float v, float inv_cell, int n) {
@@ -90,16 +71,6 @@ __device__ __forceinline__ int cell_of(float v, float inv_cell, int n) {
 __device__ __forceinline__ int cell_lo(float v, float inv_cell, int n) { return cell_of(v, inv_cell, n); }
 __device__ __forceinline__ int cell_hi(float v, float inv_cell, int n) {
   return v != v ? n - 1 : cell_of(v, inv_cell, n);
-}
-
-__device__ __forceinline__ void train_range(const WindowArgs& A, int b, int& ts, int& te) {
-  ts = 0;
-  te = A.t_cap;
-  if (A.toff) {
-    ts = clamp_row(A.toff[b], A.t_cap);
-    te = clamp_row(A.toff[b + 1], A.t_cap);
-    te = te < ts ? ts : te;
-  }
 }
 
 // ---- binning -------------------------------------------------------------------
@@ -113,7 +84,7 @@ template <bool kScatter>
 __global__ __launch_bounds__(256) void window_bin_kernel(WindowArgs A, int per_grid) {
   const int g = blockIdx.x / per_grid, blk = blockIdx.x % per_grid;
   int ts, te;
-  train_range(A, g, ts, te);
+  train_range(A.toff, g, A.t_cap, ts, te);
   int* ce = A.cell_end + (long long)g * (A.nx * A.ny + 1);
   for (long long r = ts + (long long)blk * 256 + threadIdx.x; r < te; r += (long long)per_grid * 256) {
     const float x = A.t_kpts[r].x, y = A.t_kpts[r].y;
@@ -219,7 +190,7 @@ __global__ __launch_bounds__(kWinBlock) void knn_window_kernel(WindowArgs A) {
   const int qi = (int)ql;
   const int b = seg_of(A.qoff, A.nseg, A.q_cap, qi);
   int ts, te;
-  train_range(A, b, ts, te);
+  train_range(A.toff, b, A.t_cap, ts, te);
   const int n_cells = A.nx * A.ny;
   const int* ce = A.cell_end + (A.toff ? (long long)b * (n_cells + 1) : 0ll);
 
@@ -231,7 +202,7 @@ __global__ __launch_bounds__(kWinBlock) void knn_window_kernel(WindowArgs A) {
     px = o[0];
     py = o[1];
   }
-  Best2 best{INFINITY, INFINITY, -1, -1};
+  Best2 best = top2_empty<float>();
   if (px == px && py == py) {  // a NaN position admits no row
     const float r = A.radius;
     const float sx = kWinSlack * (fabsf(px) + r), sy = kWinSlack * (fabsf(py) + r);
@@ -263,14 +234,7 @@ __global__ __launch_bounds__(kWinBlock) void knn_window_kernel(WindowArgs A) {
       }
     }
   }
-  if (sub == 0) {
-    A.idx[(long long)qi * A.k] = best.i1;
-    A.dist[(long long)qi * A.k] = best.d1;
-    if (A.k == 2) {
-      A.idx[(long long)qi * A.k + 1] = best.i2;
-      A.dist[(long long)qi * A.k + 1] = best.d2;
-    }
-  }
+  if (sub == 0) write_knn(best, qi, A.k, A.idx, A.dist);
 }
 
 }  // namespace

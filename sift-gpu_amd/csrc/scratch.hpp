@@ -1,7 +1,9 @@
 // scratch.hpp -- how the matcher, byte-matcher, windowed-matcher, cross-check, front-end and segmented-homography entry
 // points divide the context's one scratch block (sift_ctx::d_match).  Each
 // layout is described once, as a function of a Carver, and run twice: on a null
-// base to measure the block, then on the block itself.  Plain host C++ (no HIP
+// base to measure the block, then on the block itself.  The three segmented
+// matchers share one host and one cross-match layout, templates over a metric
+// tag (L1F32, L1U8, L2SqrU8).  Plain host C++ (no HIP
 // include), so that tests/cpp/scratch_layout.cpp, match_u8_layout.cpp,
 // match_l2_u8_layout.cpp, cross_check_layout.cpp, homography_layout.cpp and match_window_layout.cpp check every
 // layout without a GPU.
@@ -76,16 +78,6 @@ inline SegParts seg_layout(Carver& a, int n_segments, int q_cap, int splits) {
   return {a.take<int>((size_t)n_segments + 1), knn_parts(a, splits > 1 ? (size_t)splits * q_cap : 0)};
 }
 
-// sift_knn_match_l1_segmented: t_off keeps its place when the caller has no
-// train offsets, and is null then.
-struct SegHost { float *query, *train; int* idx; float* dist; int *q_off, *t_off; SegParts seg; };
-inline SegHost seg_host_layout(Carver& a, int n_segments, int q_cap, int t_cap, bool has_t_off, int k, int splits) {
-  return {a.take<float>((size_t)q_cap * kDescRow), a.take<float>(at_least_one(t_cap) * kDescRow),
-          a.take<int>((size_t)q_cap * k),          a.take<float>((size_t)q_cap * k),
-          a.take<int>((size_t)n_segments + 1),     a.take_if<int>(has_t_off, (size_t)n_segments + 1),
-          seg_layout(a, n_segments, q_cap, splits)};
-}
-
 // ---- 8-bit descriptors (match_u8.hip) ----
 // A byte row is kDescRow bytes.  The matcher's query tile is 64 x Q rows, but a
 // layout depends on it only through the split count the caller passes: the tile
@@ -99,19 +91,6 @@ struct SegPartsU8 { int* tile_start; KnnPartsU8 parts; };
 inline SegPartsU8 seg_u8_layout(Carver& a, int n_segments, int q_cap, int splits) {
   const size_t n = splits > 1 ? (size_t)splits * q_cap : 0;
   return {a.take<int>((size_t)n_segments + 1), {a.take<Int2>(n), a.take<Int2>(n)}};
-}
-
-// sift_knn_match_l1_u8_segmented, and sift_knn_match_l1_u8 as one segment over
-// a shared train set (the library writes q_off itself): the staged byte rows,
-// results and offsets -- t_off keeps its place when the caller has no train
-// offsets, and is null then -- then the device form's pieces.
-struct SegHostU8 { uint8_t *query, *train; int* idx; float* dist; int *q_off, *t_off; SegPartsU8 seg; };
-inline SegHostU8 seg_u8_host_layout(Carver& a, int n_segments, int q_cap, int t_cap, bool has_t_off, int k,
-                                    int splits) {
-  return {a.take<uint8_t>((size_t)q_cap * kDescRow), a.take<uint8_t>(at_least_one(t_cap) * kDescRow),
-          a.take<int>((size_t)q_cap * k),            a.take<float>((size_t)q_cap * k),
-          a.take<int>((size_t)n_segments + 1),       a.take_if<int>(has_t_off, (size_t)n_segments + 1),
-          seg_u8_layout(a, n_segments, q_cap, splits)};
 }
 
 // ---- squared L2 on 8-bit descriptors (match_l2_u8.hip) ----
@@ -128,17 +107,44 @@ inline SegPartsL2U8 seg_l2_u8_layout(Carver& a, int n_segments, int q_cap, int t
           {a.take<Int2>(n), a.take<Int2>(n)}};
 }
 
-// sift_knn_match_l2sqr_u8_segmented, and sift_knn_match_l2sqr_u8 as one segment
-// over a shared train set: seg_u8_host_layout's staging, then the device form's
-// pieces.
-struct SegHostL2U8 { uint8_t *query, *train; int* idx; float* dist; int *q_off, *t_off; SegPartsL2U8 seg; };
-inline SegHostL2U8 seg_l2_u8_host_layout(Carver& a, int n_segments, int q_cap, int t_cap, bool has_t_off, int k,
-                                         int splits) {
-  return {a.take<uint8_t>((size_t)q_cap * kDescRow), a.take<uint8_t>(at_least_one(t_cap) * kDescRow),
-          a.take<int>((size_t)q_cap * k),            a.take<float>((size_t)q_cap * k),
-          a.take<int>((size_t)n_segments + 1),       a.take_if<int>(has_t_off, (size_t)n_segments + 1),
-          seg_l2_u8_layout(a, n_segments, q_cap, t_cap, splits)};
+// ---- one description of the three segmented matchers' scratch ----
+// What a layout needs of a metric: the element type of a descriptor row and the
+// device form's pieces (the L1 forms ignore t_cap).  apps.hip adds the stage,
+// the split count and the launcher to each.
+struct L1F32 {
+  using Row = float; using Seg = SegParts;
+  static Seg layout(Carver& a, int n, int q_cap, int, int splits) { return seg_layout(a, n, q_cap, splits); }
+};
+struct L1U8 {
+  using Row = uint8_t; using Seg = SegPartsU8;
+  static Seg layout(Carver& a, int n, int q_cap, int, int splits) { return seg_u8_layout(a, n, q_cap, splits); }
+};
+struct L2SqrU8 {
+  using Row = uint8_t; using Seg = SegPartsL2U8;
+  static Seg layout(Carver& a, int n, int q_cap, int t_cap, int s) { return seg_l2_u8_layout(a, n, q_cap, t_cap, s); }
+};
+
+// The host form of a segmented matcher, and the one-segment byte forms
+// (sift_knn_match_l1_u8, _l2sqr_u8: one segment over a shared train set, the
+// library writes q_off itself): the staged rows, results and offsets -- t_off
+// keeps its place when the caller has no train offsets, and is null then --
+// then the device form's pieces.
+template <typename M>
+struct SegHostOf { typename M::Row *query, *train; int* idx; float* dist; int *q_off, *t_off; typename M::Seg seg; };
+template <typename M>
+SegHostOf<M> seg_host_layout_of(Carver& a, int n_segments, int q_cap, int t_cap, bool has_t_off, int k, int splits) {
+  using Row = typename M::Row;
+  return {a.take<Row>((size_t)q_cap * kDescRow), a.take<Row>(at_least_one(t_cap) * kDescRow),
+          a.take<int>((size_t)q_cap * k),        a.take<float>((size_t)q_cap * k),
+          a.take<int>((size_t)n_segments + 1),   a.take_if<int>(has_t_off, (size_t)n_segments + 1),
+          M::layout(a, n_segments, q_cap, t_cap, splits)};
 }
+using SegHost = SegHostOf<L1F32>;  // the names the layout tests use
+using SegHostU8 = SegHostOf<L1U8>;
+using SegHostL2U8 = SegHostOf<L2SqrU8>;
+constexpr auto seg_host_layout = seg_host_layout_of<L1F32>;
+constexpr auto seg_u8_host_layout = seg_host_layout_of<L1U8>;
+constexpr auto seg_l2_u8_host_layout = seg_host_layout_of<L2SqrU8>;
 
 // sift_descriptors_to_u8: the staged float rows, then the byte rows.
 struct QuantHostU8 { float* desc; uint8_t* out; };
@@ -201,21 +207,15 @@ inline CrossTables cross_tables(Carver& a, int q_cap, int fwd_k, int t_cap, int 
 }
 template <typename Parts>
 struct CrossMatch { CrossTables tab; Parts fwd, rev; };
-inline CrossMatch<SegParts> cross_match_layout(Carver& a, int n_segments, int q_cap, int t_cap, int fwd_k,
-                                               int fwd_splits, int rev_splits, int blocks) {
-  return {cross_tables(a, q_cap, fwd_k, t_cap, blocks), seg_layout(a, n_segments, q_cap, fwd_splits),
-          seg_layout(a, n_segments, t_cap, rev_splits)};
+template <typename M>
+CrossMatch<typename M::Seg> cross_match_layout_of(Carver& a, int n_segments, int q_cap, int t_cap, int fwd_k,
+                                                  int fwd_splits, int rev_splits, int blocks) {
+  return {cross_tables(a, q_cap, fwd_k, t_cap, blocks), M::layout(a, n_segments, q_cap, t_cap, fwd_splits),
+          M::layout(a, n_segments, t_cap, q_cap, rev_splits)};
 }
-inline CrossMatch<SegPartsU8> cross_match_u8_layout(Carver& a, int n_segments, int q_cap, int t_cap, int fwd_k,
-                                                    int fwd_splits, int rev_splits, int blocks) {
-  return {cross_tables(a, q_cap, fwd_k, t_cap, blocks), seg_u8_layout(a, n_segments, q_cap, fwd_splits),
-          seg_u8_layout(a, n_segments, t_cap, rev_splits)};
-}
-inline CrossMatch<SegPartsL2U8> cross_match_l2_u8_layout(Carver& a, int n_segments, int q_cap, int t_cap, int fwd_k,
-                                                         int fwd_splits, int rev_splits, int blocks) {
-  return {cross_tables(a, q_cap, fwd_k, t_cap, blocks), seg_l2_u8_layout(a, n_segments, q_cap, t_cap, fwd_splits),
-          seg_l2_u8_layout(a, n_segments, t_cap, q_cap, rev_splits)};
-}
+constexpr auto cross_match_layout = cross_match_layout_of<L1F32>;
+constexpr auto cross_match_u8_layout = cross_match_layout_of<L1U8>;
+constexpr auto cross_match_l2_u8_layout = cross_match_layout_of<L2SqrU8>;
 
 // ---- spatially gated matching (match_window.hip) ----
 // The search grid of sift_knn_match_window_segmented_device, from host

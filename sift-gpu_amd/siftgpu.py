@@ -521,6 +521,39 @@ class Context:
                                                      ctypes.c_void_p(idx_ptr), ctypes.c_void_p(dist_ptr)))
 
     # ---- a whole batch: segmented matcher + ratio test + point pairs -------
+    # The three metrics' segmented entry points take the same arguments: one
+    # helper per form, keyed by the C function's name.
+    def _seg_device(self, fn, query_ptr, q_offsets_ptr, n_segments, q_cap, train_ptr, t_offsets_ptr, t_cap, k, idx_ptr,
+                    dist_ptr):
+        vp = ctypes.c_void_p
+        self._check(fn, getattr(self._L, fn)(self.h, vp(query_ptr), vp(q_offsets_ptr), n_segments, q_cap, vp(train_ptr),
+                                             vp(t_offsets_ptr or None), t_cap, k, vp(idx_ptr), vp(dist_ptr)))
+
+    @staticmethod
+    def _rows_arg(a):  # float rows go as float*, byte rows as void*
+        return _fp(a) if a.dtype == np.float32 else a.ctypes.data
+
+    def _seg_host(self, fn, q, q_offsets, t, t_offsets, k):
+        qo = np.ascontiguousarray(q_offsets, np.int32)
+        to = None if t_offsets is None else np.ascontiguousarray(t_offsets, np.int32)
+        if qo.ndim != 1 or len(qo) < 1 or (to is not None and to.shape != qo.shape):
+            raise ValueError("offsets must be 1-D, n_segments + 1 entries each")
+        pint = ctypes.POINTER(ctypes.c_int)
+        idx = np.full((len(q), k), -1, np.int32)
+        dist = np.full((len(q), k), np.inf, np.float32)
+        self._check(fn, getattr(self._L, fn)(
+            self.h, self._rows_arg(q), qo.ctypes.data_as(pint), len(qo) - 1, len(q), self._rows_arg(t),
+            None if to is None else to.ctypes.data_as(pint), len(t), k, idx.ctypes.data_as(pint), _fp(dist)))
+        return idx, dist
+
+    def _one_seg_u8(self, fn, query, train, k):
+        q, t = self._u8_rows(query), self._u8_rows(train)
+        idx = np.empty((len(q), k), np.int32)
+        dist = np.empty((len(q), k), np.float32)
+        self._check(fn, getattr(self._L, fn)(self.h, q.ctypes.data, len(q), t.ctypes.data, len(t), k,
+                                             idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _fp(dist)))
+        return idx, dist
+
     def knn_match_segmented_device(self, query_ptr: int, q_offsets_ptr: int, n_segments: int, q_cap: int,
                                    train_ptr: int, t_offsets_ptr: int | None, t_cap: int, k: int, idx_ptr: int,
                                    dist_ptr: int):
@@ -529,11 +562,8 @@ class Context:
         q_cap / t_cap; t_offsets_ptr None = one shared train set.  Consecutive
         frames of a batch: train_ptr = query_ptr, t_offsets_ptr = q_offsets_ptr + 4,
         n_segments = batch - 1."""
-        self._check("sift_knn_match_l1_segmented_device",
-                    self._L.sift_knn_match_l1_segmented_device(
-                        self.h, ctypes.c_void_p(query_ptr), ctypes.c_void_p(q_offsets_ptr), n_segments, q_cap,
-                        ctypes.c_void_p(train_ptr), ctypes.c_void_p(t_offsets_ptr or None), t_cap, k,
-                        ctypes.c_void_p(idx_ptr), ctypes.c_void_p(dist_ptr)))
+        self._seg_device("sift_knn_match_l1_segmented_device", query_ptr, q_offsets_ptr, n_segments, q_cap, train_ptr,
+                         t_offsets_ptr, t_cap, k, idx_ptr, dist_ptr)
 
     def ratio_matches_device(self, idx_ptr: int, dist_ptr: int, q_offsets_ptr: int, n_segments: int, q_cap: int,
                              ratio: float, q_kpts_ptr: int | None, t_kpts_ptr: int | None,
@@ -555,19 +585,7 @@ class Context:
         [q_offsets[0], q_offsets[-1]) keep idx -1 / dist +inf."""
         q = np.ascontiguousarray(query, np.float32).reshape(-1, DESC_LEN)
         t = np.ascontiguousarray(train, np.float32).reshape(-1, DESC_LEN)
-        qo = np.ascontiguousarray(q_offsets, np.int32)
-        to = None if t_offsets is None else np.ascontiguousarray(t_offsets, np.int32)
-        if qo.ndim != 1 or len(qo) < 1 or (to is not None and to.shape != qo.shape):
-            raise ValueError("offsets must be 1-D, n_segments + 1 entries each")
-        pint = ctypes.POINTER(ctypes.c_int)
-        idx = np.full((len(q), k), -1, np.int32)
-        dist = np.full((len(q), k), np.inf, np.float32)
-        self._check("sift_knn_match_l1_segmented",
-                    self._L.sift_knn_match_l1_segmented(
-                        self.h, _fp(q), qo.ctypes.data_as(pint), len(qo) - 1, len(q), _fp(t),
-                        None if to is None else to.ctypes.data_as(pint), len(t), k, idx.ctypes.data_as(pint),
-                        _fp(dist)))
-        return idx, dist
+        return self._seg_host("sift_knn_match_l1_segmented", q, q_offsets, t, t_offsets, k)
 
     def ratioMatches(self, idx: np.ndarray, dist: np.ndarray, q_offsets, ratio: float = 0.86, q_kpts=None,
                      t_kpts=None, t_offsets=None):
@@ -627,11 +645,8 @@ class Context:
         """knn_match_segmented_device on uint8 rows (no sync): same arguments and
         contract; dist stays float32 and holds the exact integer distance, so
         ratio_matches_device takes the output unchanged."""
-        self._check("sift_knn_match_l1_u8_segmented_device",
-                    self._L.sift_knn_match_l1_u8_segmented_device(
-                        self.h, ctypes.c_void_p(query_ptr), ctypes.c_void_p(q_offsets_ptr), n_segments, q_cap,
-                        ctypes.c_void_p(train_ptr), ctypes.c_void_p(t_offsets_ptr or None), t_cap, k,
-                        ctypes.c_void_p(idx_ptr), ctypes.c_void_p(dist_ptr)))
+        self._seg_device("sift_knn_match_l1_u8_segmented_device", query_ptr, q_offsets_ptr, n_segments, q_cap, train_ptr,
+                         t_offsets_ptr, t_cap, k, idx_ptr, dist_ptr)
 
     @staticmethod
     def _u8_rows(a):
@@ -643,31 +658,12 @@ class Context:
     def knnMatchU8Segmented(self, query: np.ndarray, q_offsets, train: np.ndarray, t_offsets=None, k: int = 2):
         """knnMatchSegmented on uint8 descriptors (host arrays): idx int32, dist
         float32 (integer-valued) [len(query), k]."""
-        q, t = self._u8_rows(query), self._u8_rows(train)
-        qo = np.ascontiguousarray(q_offsets, np.int32)
-        to = None if t_offsets is None else np.ascontiguousarray(t_offsets, np.int32)
-        if qo.ndim != 1 or len(qo) < 1 or (to is not None and to.shape != qo.shape):
-            raise ValueError("offsets must be 1-D, n_segments + 1 entries each")
-        pint = ctypes.POINTER(ctypes.c_int)
-        idx = np.full((len(q), k), -1, np.int32)
-        dist = np.full((len(q), k), np.inf, np.float32)
-        self._check("sift_knn_match_l1_u8_segmented",
-                    self._L.sift_knn_match_l1_u8_segmented(
-                        self.h, q.ctypes.data, qo.ctypes.data_as(pint), len(qo) - 1, len(q), t.ctypes.data,
-                        None if to is None else to.ctypes.data_as(pint), len(t), k, idx.ctypes.data_as(pint),
-                        _fp(dist)))
-        return idx, dist
+        return self._seg_host("sift_knn_match_l1_u8_segmented", self._u8_rows(query), q_offsets, self._u8_rows(train), t_offsets, k)
 
     def knnMatchU8(self, query: np.ndarray, train: np.ndarray, k: int = 2):
         """knnMatch on uint8 descriptors: idx int32, dist float32 (integer-valued)
         [n_query, k]; idx -1 / dist +inf where there are fewer than k train rows."""
-        q, t = self._u8_rows(query), self._u8_rows(train)
-        idx = np.empty((len(q), k), np.int32)
-        dist = np.empty((len(q), k), np.float32)
-        self._check("sift_knn_match_l1_u8",
-                    self._L.sift_knn_match_l1_u8(self.h, q.ctypes.data, len(q), t.ctypes.data, len(t), k,
-                                                 idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _fp(dist)))
-        return idx, dist
+        return self._one_seg_u8("sift_knn_match_l1_u8", query, train, k)
 
     # ---- squared L2 on 8-bit descriptors (integer MFMA; opt-in) ----------------
     def knn_match_l2sqr_u8_segmented_device(self, query_ptr: int, q_offsets_ptr: int, n_segments: int, q_cap: int,
@@ -677,41 +673,19 @@ class Context:
         same arguments and contract; dist is float32 and holds the exact integer
         sum of (q - t)^2, at most 8,323,200.  No square root is taken: pass
         ratio * ratio to ratio_matches_device (0.86 ** 2 for the usual 0.86)."""
-        self._check("sift_knn_match_l2sqr_u8_segmented_device",
-                    self._L.sift_knn_match_l2sqr_u8_segmented_device(
-                        self.h, ctypes.c_void_p(query_ptr), ctypes.c_void_p(q_offsets_ptr), n_segments, q_cap,
-                        ctypes.c_void_p(train_ptr), ctypes.c_void_p(t_offsets_ptr or None), t_cap, k,
-                        ctypes.c_void_p(idx_ptr), ctypes.c_void_p(dist_ptr)))
+        self._seg_device("sift_knn_match_l2sqr_u8_segmented_device", query_ptr, q_offsets_ptr, n_segments, q_cap, train_ptr,
+                         t_offsets_ptr, t_cap, k, idx_ptr, dist_ptr)
 
     def knnMatchL2SqrU8Segmented(self, query: np.ndarray, q_offsets, train: np.ndarray, t_offsets=None, k: int = 2):
         """knnMatchU8Segmented with the squared L2 distance (host arrays): idx
         int32, dist float32 (integer-valued, squared) [len(query), k]."""
-        q, t = self._u8_rows(query), self._u8_rows(train)
-        qo = np.ascontiguousarray(q_offsets, np.int32)
-        to = None if t_offsets is None else np.ascontiguousarray(t_offsets, np.int32)
-        if qo.ndim != 1 or len(qo) < 1 or (to is not None and to.shape != qo.shape):
-            raise ValueError("offsets must be 1-D, n_segments + 1 entries each")
-        pint = ctypes.POINTER(ctypes.c_int)
-        idx = np.full((len(q), k), -1, np.int32)
-        dist = np.full((len(q), k), np.inf, np.float32)
-        self._check("sift_knn_match_l2sqr_u8_segmented",
-                    self._L.sift_knn_match_l2sqr_u8_segmented(
-                        self.h, q.ctypes.data, qo.ctypes.data_as(pint), len(qo) - 1, len(q), t.ctypes.data,
-                        None if to is None else to.ctypes.data_as(pint), len(t), k, idx.ctypes.data_as(pint),
-                        _fp(dist)))
-        return idx, dist
+        return self._seg_host("sift_knn_match_l2sqr_u8_segmented", self._u8_rows(query), q_offsets, self._u8_rows(train), t_offsets, k)
 
     def knnMatchL2SqrU8(self, query: np.ndarray, train: np.ndarray, k: int = 2):
         """knnMatchU8 with the squared L2 distance: idx int32, dist float32
         (integer-valued, squared) [n_query, k]; idx -1 / dist +inf where there
         are fewer than k train rows."""
-        q, t = self._u8_rows(query), self._u8_rows(train)
-        idx = np.empty((len(q), k), np.int32)
-        dist = np.empty((len(q), k), np.float32)
-        self._check("sift_knn_match_l2sqr_u8",
-                    self._L.sift_knn_match_l2sqr_u8(self.h, q.ctypes.data, len(q), t.ctypes.data, len(t), k,
-                                                    idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _fp(dist)))
-        return idx, dist
+        return self._one_seg_u8("sift_knn_match_l2sqr_u8", query, train, k)
 
     # ---- matching within a search window (spatially gated kNN) for a whole batch ----
     def knn_match_window_segmented_device(self, metric: int, query_ptr: int, q_kpts_ptr: int, q_offsets_ptr: int,

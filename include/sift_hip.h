@@ -475,6 +475,73 @@ int sift_upsample2x(sift_ctx* ctx, const float* src, int rows, int cols, size_t 
 int sift_upsample2x_device(sift_ctx* ctx, const float* d_src, int batch, int rows, int cols, size_t row_stride,
                            size_t img_stride, float* d_dst, size_t out_row_stride, size_t out_img_stride);
 
+/* ---- warpPerspective of a whole batch (the call after the homography) -------
+ * dst = cv::warpPerspective(src, dst, H, Size(out_cols, out_rows),
+ *                           INTER_LINEAR [| WARP_INVERSE_MAP], BORDER_CONSTANT, 0)
+ * on CV_32FC1 (SIFT_PIXEL_F32, channels 1), CV_8UC1 and CV_8UC3 (SIFT_PIXEL_U8,
+ * channels 1 or 3, interleaved), stated here as the library's own rule
+ * (csrc/warp_math.hpp, which host and device both compile; restated in numpy in
+ * tests/warp_inputs.py); parity against OpenCV itself is by construction and
+ * unpinned, as for sift_upsample2x and the homography (no OpenCV here).
+ * The matrix M, in double: with SIFT_WARP_INVERSE_MAP M = H; otherwise
+ * M = adj(H) * (1 / det(H)) with
+ *     c0 = h4 h8 - h5 h7,  c1 = h5 h6 - h3 h8,  c2 = h3 h7 - h4 h6,
+ *     det = (h0 c0 + h1 c1) + h2 c2,  r = 1 / det,
+ *     M0 = c0 r,  M1 = (h2 h7 - h1 h8) r,  M2 = (h1 h5 - h2 h4) r,
+ *     M3 = c1 r,  M4 = (h0 h8 - h2 h6) r,  M5 = (h2 h3 - h0 h5) r,
+ *     M6 = c2 r,  M7 = (h1 h6 - h0 h7) r,  M8 = (h0 h4 - h1 h3) r
+ * (each product difference two multiplies and one subtract, never fused).
+ * A segment warps to nothing -- every destination pixel is 0 -- when
+ * d_found[b] == 0, when an entry of H or of M is not finite, or when det is 0
+ * or not finite: sift_perspective_transform_segmented_device's convention.
+ * The source position of destination pixel (x, y), in double:
+ *     Wd = (M6 x + M7 y) + M8,  W = Wd != 0 ? 32.0 / Wd : 0.0,
+ *     fX = ((M0 x + M1 y) + M2) W,  fY = ((M3 x + M4 y) + M5) W;
+ * a NaN fX or fY makes the pixel 0; otherwise each is clamped to
+ * [INT_MIN, INT_MAX], X = (int)rint(fX), Y = (int)rint(fY) (ties to even),
+ * sx = X >> 5, ax = X & 31, sy = Y >> 5, ay = Y & 31 (arithmetic shifts).
+ * The samples v00 = S[sy][sx], v01 = S[sy][sx + 1], v10 = S[sy + 1][sx],
+ * v11 = S[sy + 1][sx + 1]; a sample outside [0, rows) x [0, cols) is the value
+ * 0 and is never read, each sample on its own.
+ * f32: fx = ax * 0.03125f, fy = ay * 0.03125f, w00 = (1 - fy) * (1 - fx),
+ * w01 = (1 - fy) * fx, w10 = fy * (1 - fx), w11 = fy * fx (exact multiples of
+ * 1/1024), out = ((v00 * w00 + v01 * w01) + v10 * w10) + v11 * w11: four
+ * multiplies and three adds in that order, never fused.  Denormals are not
+ * flushed; a NaN or infinite sample inside the image propagates, even at
+ * weight 0.
+ * u8, each channel alone: k00 = (32 - ay) * (32 - ax), k01 = (32 - ay) * ax,
+ * k10 = ay * (32 - ax), k11 = ay * ax (sum 1024),
+ * out = (v00 k00 + v01 k01 + v10 k10 + v11 k11 + 512) >> 10 -- OpenCV's 15-bit
+ * coefficient table with the common factor 32 taken out.
+ * Errors: a NULL context or buffer (d_found may be NULL: all found), a dimension
+ * < 1, a pixel / channels pair other than the three above, an unknown flag, a
+ * stride too small for its row or image, or an f32 stride or pointer that is not
+ * a multiple of 4: SIFT_E_INVALID; a dimension above 2^30: SIFT_E_SIZE.  The
+ * context's creation limits do not apply.  Under SIFT_FLAG_PROFILE the stage is
+ * "warp" (8 algorithmic bytes per f32 destination pixel, 2 or 6 per u8 pixel). */
+#define SIFT_WARP_INVERSE_MAP 0x1u
+#define SIFT_PIXEL_F32 0
+#define SIFT_PIXEL_U8 1
+/* Device buffers, enqueued on the context stream with no synchronisation, one
+ * launch, no scratch.  Image b is warped by H[b]: d_H is [n_segments][9]
+ * doubles and d_found [n_segments] ints, exactly what
+ * sift_find_homography_segmented_device leaves.  Strides in bytes, 0 = packed;
+ * img_stride == 0 with n_segments > 1 is one source image warped by every H.
+ * Only the out_rows x out_cols pixels of each destination image are written --
+ * row and image padding keep their bytes.  Destination rows that are 16-byte
+ * aligned (u8: 4-byte) are written with 16-byte (dword) stores.  n_segments
+ * == 0: SIFT_OK, nothing enqueued. */
+int sift_warp_perspective_segmented_device(sift_ctx* ctx, int pixel, int channels, const void* d_src, int rows,
+                                           int cols, size_t row_stride, size_t img_stride, const double* d_H,
+                                           const int* d_found /* may be NULL: all found */, int n_segments,
+                                           unsigned flags, void* d_dst, int out_rows, int out_cols,
+                                           size_t out_row_stride, size_t out_img_stride);
+/* Host buffers (synchronous), one image: only the bytes a strided view owns
+ * are read; dst is out_rows x out_cols pixels, packed.  SIFT_E_INVALID with dst
+ * zeroed if H warps to nothing. */
+int sift_warp_perspective(sift_ctx* ctx, int pixel, int channels, const void* src, int rows, int cols,
+                          size_t row_stride, const double* H, unsigned flags, void* dst, int out_rows, int out_cols);
+
 /* ---- matching ------------------------------------------ */
 /* Replaces `BFMatcher(NORM_L1).knnMatch(query, train, matches, k)` of the
  * reference application (src/main.cpp:25-27; the 0.86 ratio test at :28-40

@@ -3,16 +3,19 @@
 // L1, byte L1, byte squared L2), the windowed matcher, the ratio test with
 // point pairs, the cross-check stage with its one-call form, the BGR8 front
 // end and the doubled image, each in a device and a host form, the one-pair
-// homography wrappers and the segmented homography and corner transform.  Host
-// code only; the kernels live in match.hip, match_u8.hip, match_l2_u8.hip,
-// match_window.hip, cross_check.hip, frontend.hip, upsample.hip and
-// homography_batch.hip (the one-pair homography is host code in
-// homography.hip).  The segmented matchers are one path, written once as
+// homography wrappers, the segmented homography and corner transform, and the
+// perspective warp of a batch.  Host code only; the kernels live in match.hip,
+// match_u8.hip, match_l2_u8.hip, match_window.hip, cross_check.hip,
+// frontend.hip, upsample.hip, homography_batch.hip and warp.hip (the one-pair
+// homography is host code in homography.hip).  The segmented matchers are one path, written once as
 // function templates over a metric tag (MatchL1F32, MatchL1U8, MatchL2SqrU8);
 // their extern "C" entry points only forward.  Every form carves its scratch
 // from the context's one block by a layout of scratch.hpp.
+#include <cstring>
+
 #include "ctx.hpp"
 #include "scratch.hpp"
+#include "warp_math.hpp"
 
 using namespace sift;
 
@@ -419,6 +422,22 @@ int check_bgr(sift_ctx* c, const void* bgr, int batch, int rows, int cols, int o
   if (!bgr || !gray) return fail(c, SIFT_E_INVALID, "null buffer");
   if (batch < 1 || rows < 1 || cols < 1 || out_rows < 1 || out_cols < 1)
     return fail(c, SIFT_E_INVALID, "empty image");
+  return SIFT_OK;
+}
+
+// ---- warpPerspective of a batch (warp.hip, warp_math.hpp) ----
+// The checks the device and the host form share; bpp: bytes per pixel.
+int check_warp(sift_ctx* c, int pixel, int channels, const void* src, int rows, int cols, const double* H,
+               unsigned flags, const void* dst, int out_rows, int out_cols, size_t* bpp) {
+  if (!c) return SIFT_E_INVALID;
+  if (!(pixel == SIFT_PIXEL_F32 && channels == 1) && !(pixel == SIFT_PIXEL_U8 && (channels == 1 || channels == 3)))
+    return fail(c, SIFT_E_INVALID, "pixel / channels must be F32 x 1, U8 x 1 or U8 x 3");
+  if (flags & ~SIFT_WARP_INVERSE_MAP) return fail(c, SIFT_E_INVALID, "unknown warp flag");
+  if (!src || !H || !dst) return fail(c, SIFT_E_INVALID, "null buffer");
+  if (rows < 1 || cols < 1 || out_rows < 1 || out_cols < 1) return fail(c, SIFT_E_INVALID, "empty image");
+  if (rows > (1 << 30) || cols > (1 << 30) || out_rows > (1 << 30) || out_cols > (1 << 30))
+    return fail(c, SIFT_E_SIZE, "a dimension exceeds 2^30");
+  *bpp = pixel == SIFT_PIXEL_F32 ? sizeof(float) : (size_t)channels;
   return SIFT_OK;
 }
 
@@ -852,6 +871,71 @@ int sift_perspective_transform_segmented_device(sift_ctx* c, const double* d_H, 
     launch_perspective_seg(c->stream, d_H, d_found, n_segments, d_xy, n_pts, d_out_xy);
   }
   HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
+// ---- warpPerspective of every image of a batch by its own homography (warp.hip) ----
+int sift_warp_perspective_segmented_device(sift_ctx* c, int pixel, int channels, const void* d_src, int rows, int cols,
+                                           size_t row_stride, size_t img_stride, const double* d_H,
+                                           const int* d_found, int n_segments, unsigned flags, void* d_dst,
+                                           int out_rows, int out_cols, size_t out_row_stride,
+                                           size_t out_img_stride) {
+  if (!c) return SIFT_E_INVALID;
+  if (n_segments < 0) return fail(c, SIFT_E_INVALID, "negative count");
+  if (n_segments == 0) return SIFT_OK;
+  size_t bpp = 0;
+  if (int rc = check_warp(c, pixel, channels, d_src, rows, cols, d_H, flags, d_dst, out_rows, out_cols, &bpp))
+    return rc;
+  if (row_stride == 0) row_stride = (size_t)cols * bpp;
+  if (out_row_stride == 0) out_row_stride = (size_t)out_cols * bpp;
+  if (out_img_stride == 0) out_img_stride = out_row_stride * out_rows;
+  if (row_stride < (size_t)cols * bpp || (img_stride != 0 && n_segments > 1 && img_stride < row_stride * rows))
+    return fail(c, SIFT_E_INVALID, "source strides too small");
+  if (out_row_stride < (size_t)out_cols * bpp || (n_segments > 1 && out_img_stride < out_row_stride * out_rows))
+    return fail(c, SIFT_E_INVALID, "output strides too small");
+  if (pixel == SIFT_PIXEL_F32 &&
+      ((row_stride | img_stride | out_row_stride | out_img_stride) % sizeof(float) ||
+       ((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst)) % sizeof(float))))
+    return fail(c, SIFT_E_INVALID, "float buffers and strides must be multiples of 4 bytes");
+  (void)hipSetDevice(c->device);
+  {
+    StageScope s(c, ST_WARP, 0, 2.0 * bpp * out_rows * (double)out_cols * n_segments);
+    launch_warp_perspective(c->stream, pixel == SIFT_PIXEL_U8, channels, d_src, (long long)row_stride,
+                            (long long)img_stride, rows, cols, d_H, d_found, n_segments,
+                            (flags & SIFT_WARP_INVERSE_MAP) != 0, d_dst, (long long)out_row_stride,
+                            (long long)out_img_stride, out_rows, out_cols);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
+int sift_warp_perspective(sift_ctx* c, int pixel, int channels, const void* src, int rows, int cols, size_t row_stride,
+                          const double* H, unsigned flags, void* dst, int out_rows, int out_cols) {
+  size_t bpp = 0;
+  int rc = check_warp(c, pixel, channels, src, rows, cols, H, flags, dst, out_rows, out_cols, &bpp);
+  if (rc) return rc;
+  if (row_stride == 0) row_stride = (size_t)cols * bpp;
+  if (row_stride < (size_t)cols * bpp || (pixel == SIFT_PIXEL_F32 && row_stride % sizeof(float)))
+    return fail(c, SIFT_E_INVALID, "row stride too small for its row, or a float stride not a multiple of 4 bytes");
+  const size_t out_row = (size_t)out_cols * bpp, out_bytes = out_row * out_rows;
+  double M[9];
+  if (!wmath::warp_matrix(H, (flags & SIFT_WARP_INVERSE_MAP) != 0, M)) {  // the kernel's own rule: nothing to run
+    memset(dst, 0, out_bytes);
+    return fail(c, SIFT_E_INVALID, "the homography warps to nothing (singular or non-finite)");
+  }
+  (void)hipSetDevice(c->device);
+  WarpHost S;  // the matcher's scratch doubles as staging here
+  if ((rc = carve(c, &S, [&](Carver& a) { return warp_host_layout(a, rows, row_stride, out_rows, out_row); })))
+    return rc;
+  // a strided view (an ROI) owns no padding after its last row: copy only what the image owns
+  const size_t owned = (size_t)(rows - 1) * row_stride + (size_t)cols * bpp;
+  HIP_TRY(c, hipMemcpyAsync(S.src, src, owned, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.H, H, 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if ((rc = sift_warp_perspective_segmented_device(c, pixel, channels, S.src, rows, cols, row_stride, 0, S.H, nullptr,
+                                                   1, flags, S.dst, out_rows, out_cols, out_row, 0)))
+    return rc;
+  HIP_TRY(c, hipMemcpyAsync(dst, S.dst, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return SIFT_OK;
 }
 

@@ -269,6 +269,13 @@ void launch_bgr8_gray(hipStream_t st, const uint8_t* src, long long sstride, lon
 // 2 rows x 2 cols destination pixels of each image and nothing else.
 void launch_upsample2x(hipStream_t st, const float* src, long long spitch, long long simg, int rows, int cols,
                        float* dst, long long dpitch, long long dimg, int batch);
+// warp.hip: warpPerspective of every image of a batch by its own homography
+// (warp_math.hpp's rule); strides in bytes, simg 0 = one source for every H,
+// found may be null.  Writes the orows x ocols destination pixels of each image
+// and nothing else.
+void launch_warp_perspective(hipStream_t st, bool u8, int channels, const void* src, long long spitch, long long simg,
+                             int rows, int cols, const double* H, const int* found, int n_segments, bool inverse,
+                             void* dst, long long dpitch, long long dimg, int orows, int ocols);
 int find_homography_ransac(const float* src_xy, const float* dst_xy, int n, double thr, int max_iters,
                            double confidence, double* H, unsigned char* mask_out);
 void perspective_transform(const double* H, const float* xy, int n, float* out);

@@ -61,7 +61,8 @@ class Buf {
   X(ST_MATCH_L2_U8, "match_l2sqr_u8_segmented") X(ST_SELECT, "select_best")                               \
   X(ST_CROSS, "cross_check_matches") X(ST_DETMASK, "detect_mask") X(ST_GRAD, "gradient")                \
   X(ST_COMPUTE_PREP, "compute_prep") X(ST_WINDOW_BIN, "match_window_bin")                              \
-  X(ST_MATCH_WINDOW, "match_window_segmented") X(ST_UPSAMPLE, "upsample2x")
+  X(ST_MATCH_WINDOW, "match_window_segmented") X(ST_UPSAMPLE, "upsample2x")                \
+  X(ST_WARP, "warp")
 enum Stage {
 #define X(id, name) id,
   SIFT_STAGES(X)

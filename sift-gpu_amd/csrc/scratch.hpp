@@ -279,6 +279,12 @@ inline UpsampleHost upsample_host_layout(Carver& a, int rows, int cols, size_t r
   return {a.take<float>((size_t)rows * row_stride), a.take<float>((size_t)4 * rows * cols)};
 }
 
+// sift_warp_perspective: the strided source rows (in bytes), the homography, then the packed warped image.
+struct WarpHost { uint8_t* src; double* H; uint8_t* dst; };
+inline WarpHost warp_host_layout(Carver& a, int rows, size_t row_stride, int out_rows, size_t out_row_bytes) {
+  return {a.take<uint8_t>((size_t)rows * row_stride), a.take<double>(9), a.take<uint8_t>((size_t)out_rows * out_row_bytes)};
+}
+
 // sift_find_homography_segmented_device (homography_batch.hip): per segment one
 // round of kHomogRound hypotheses -- the accepted 4-point subsets, their models
 // and inlier counts (-1: no model) -- then the state the RANSAC kernel hands to

@@ -39,6 +39,9 @@ N_SCALES, N_DOG, DESC_LEN = 5, 4, 128
 HOMOGRAPHY_ROUND = 64  # hypotheses per round of the segmented homography (scratch.hpp kHomogRound)
 # sift_cross_match_segmented_device's metric: the distance and the type of the descriptor rows
 SIFT_METRIC_L1_F32, SIFT_METRIC_L1_U8, SIFT_METRIC_L2SQR_U8 = 0, 1, 2
+# sift_warp_perspective[_segmented_device]: the pixel type and the flag
+SIFT_PIXEL_F32, SIFT_PIXEL_U8 = 0, 1
+SIFT_WARP_INVERSE_MAP = 0x1
 
 KEYPOINT_DTYPE = np.dtype(
     [("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
@@ -94,6 +97,10 @@ def lib():
             "sift_set_upsample": (ip, [vp, ip]),
             "sift_upsample2x": (ip, [vp, fp, ip, ip, sz, fp]),
             "sift_upsample2x_device": (ip, [vp, vp, ip, ip, ip, sz, sz, vp, sz, sz]),
+            "sift_warp_perspective_segmented_device": (ip, [vp, ip, ip, vp, ip, ip, sz, sz, vp, vp, ip, ctypes.c_uint,
+                                                            vp, ip, ip, sz, sz]),
+            "sift_warp_perspective": (ip, [vp, ip, ip, vp, ip, ip, sz, ctypes.POINTER(ctypes.c_double),
+                                           ctypes.c_uint, vp, ip, ip]),
             "sift_version": (ctypes.c_char_p, []),
             "sift_graph_stats": (ip, [vp, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong),
                                       ctypes.POINTER(ctypes.c_longlong)]),
@@ -177,7 +184,8 @@ def lib():
                     "sift_multi_set_max_features", "sift_detect_compute_masked", "sift_detect_compute_batch_masked",
                     "sift_multi_step_masked", "sift_compute_batch", "sift_compute",
                     "sift_knn_match_window_segmented_device", "sift_knn_match_window_segmented",
-                    "sift_set_upsample", "sift_upsample2x", "sift_upsample2x_device"}  # absent from older builds (A/B runs against a saved library)
+                    "sift_set_upsample", "sift_upsample2x", "sift_upsample2x_device",
+                    "sift_warp_perspective_segmented_device", "sift_warp_perspective"}  # absent from older builds (A/B runs against a saved library)
         for name, (res, args) in sigs.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -455,6 +463,46 @@ class Context:
                     self._L.sift_upsample2x_device(self.h, ctypes.c_void_p(src_ptr), batch, rows, cols, row_stride,
                                                    img_stride, ctypes.c_void_p(dst_ptr), out_row_stride,
                                                    out_img_stride))
+
+    def warpPerspective(self, img: np.ndarray, H, dsize, inverse: bool = False) -> np.ndarray:
+        """cv::warpPerspective(img, H, dsize, INTER_LINEAR [| WARP_INVERSE_MAP], BORDER_CONSTANT, 0)
+        by the rule in include/sift_hip.h (sift_warp_perspective).  img: float32 H x W, or uint8
+        H x W / H x W x 3; dsize = (width, height) as in OpenCV; the result has img's dtype and
+        channels.  An H that warps to nothing (singular, non-finite) raises SiftError with
+        SIFT_E_INVALID."""
+        img = np.asarray(img)
+        if img.dtype == np.float32 and img.ndim == 2:
+            pixel, ch = SIFT_PIXEL_F32, 1
+        elif img.dtype == np.uint8 and (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
+            pixel, ch = SIFT_PIXEL_U8, 1 if img.ndim == 2 else 3
+        else:
+            raise ValueError("expected a float32 H x W or a uint8 H x W / H x W x 3 image")
+        img = np.ascontiguousarray(img)
+        Hd = np.ascontiguousarray(H, np.float64).reshape(9)
+        oc, orows = int(dsize[0]), int(dsize[1])
+        if oc < 1 or orows < 1:
+            raise ValueError("dsize must be (width, height), both at least 1")
+        out = np.empty((orows, oc) if img.ndim == 2 else (orows, oc, 3), img.dtype)
+        r, c = img.shape[:2]
+        self._check("sift_warp_perspective",
+                    self._L.sift_warp_perspective(self.h, pixel, ch, img.ctypes.data, r, c, 0,
+                                                  Hd.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                  SIFT_WARP_INVERSE_MAP if inverse else 0, out.ctypes.data, orows, oc))
+        return out
+
+    def warp_perspective_segmented_device(self, pixel: int, channels: int, src_ptr: int, rows: int, cols: int,
+                                          row_stride: int, img_stride: int, H_ptr: int, found_ptr: int,
+                                          n_segments: int, flags: int, dst_ptr: int, out_rows: int, out_cols: int,
+                                          out_row_stride: int = 0, out_img_stride: int = 0):
+        """Device-pointer form (no sync): image b warped by H[b] ([n_segments][9] doubles, found_ptr
+        [n_segments] ints or 0), exactly what find_homography_segmented_device leaves.  Strides in
+        bytes, 0 = packed; img_stride 0 = one source image for every H."""
+        vp = ctypes.c_void_p
+        self._check("sift_warp_perspective_segmented_device",
+                    self._L.sift_warp_perspective_segmented_device(
+                        self.h, pixel, channels, vp(src_ptr), rows, cols, row_stride, img_stride, vp(H_ptr),
+                        vp(found_ptr or None), n_segments, flags, vp(dst_ptr), out_rows, out_cols, out_row_stride,
+                        out_img_stride))
 
     def calDescriptor(self, gpyr, keypoints: np.ndarray, firstOctave: int = 0) -> np.ndarray:
         r, c = gpyr[0].shape
@@ -1316,3 +1364,15 @@ def perspectiveTransform(points, H):
     if rc != SIFT_OK:
         raise SiftError("sift_perspective_transform", rc, "bad argument")
     return out
+
+
+WARP_INVERSE_MAP = 16  # cv::WARP_INVERSE_MAP
+
+
+def warpPerspective(src, M, dsize, flags: int = 0):
+    """cv::warpPerspective(src, M, dsize, flags) with INTER_LINEAR (flags 0 or 1), BORDER_CONSTANT
+    and a zero border value; flags may add WARP_INVERSE_MAP.  src: float32 H x W, or uint8 H x W /
+    H x W x 3; dsize = (width, height).  On the GPU (warp.hip) by the rule in include/sift_hip.h."""
+    if flags & ~(WARP_INVERSE_MAP | 1):
+        raise ValueError("only INTER_LINEAR, optionally with WARP_INVERSE_MAP, is implemented")
+    return _ctx(1, 1).warpPerspective(src, M, dsize, inverse=bool(flags & WARP_INVERSE_MAP))

@@ -681,7 +681,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void bl
 }
 
 // The same launch without plane 4 (SIFT_NCL's sparse flow: detection takes
-// the widest scale point by point, detect.hip's g4_fill_kernel): slot s blurs
+// the widest scale point by point, refine.hip's g4_fill_kernel): slot s blurs
 // scale 3 - s.  Its own kernel, so that no w = 18 walk is instantiated: the
 // walks left need 70 VGPRs.  The register hold keeps the 3 waves per SIMD of
 // the four-slot kernel on purpose -- the finding above is about the

@@ -403,9 +403,10 @@ FastPlan fast_plan(int columns, int rows, int slots, int halo);
 // fills the chip with the batch variants.  SIFT_HIP_ONE_IMAGE_PX overrides the
 // limit (A/B runs).
 constexpr long long kOneImagePx = 4ll << 20;
-bool one_image_variants(const Layout& L, int batch);
+bool one_image_variants(const Layout& L, int batch);  // orient.hip
 
-// detect.hip
+// The detection stages: extrema.hip, scan.hip, refine.hip, orient.hip, emit.hip
+// (what only they share is in detect_args.hpp)
 struct DetectBufs {
   unsigned* mask;       // candidate bitmask, mask_words_per_image * batch
   int* blk_counts;      // per scan block
@@ -447,13 +448,15 @@ struct SparseG4 {
   const float* coef4;
   int grid;
 };
-int scan_tiles_for(long long cap);
+int scan_tiles_for(long long cap);  // scan.hip
+// extrema.hip
 long long mask_words_per_image(const Layout& L);
 int mask_blocks_per_image(const Layout& L);
 void launch_extrema(hipStream_t st, const Layout& L, const float* gpyr, float* dog, bool write_dog,
                     float2* grad, const MathConsts* mc, int batch, DetectBufs& D, unsigned sparse = 0);
 void launch_grad(hipStream_t st, const Layout& L, const float* gpyr, float2* grad, int batch, int s_lo,
                  int s_hi, const MathConsts* mc);
+// refine.hip (refinement, then orient.hip's launch_orient)
 void launch_refine_orient(hipStream_t st, const Layout& L, const float* gpyr, const float2* grad,
                           const float* dog, const MathConsts* mc, DetectBufs& D, int batch,
                           SparseG4 sp = SparseG4{0, nullptr, 0});
@@ -462,6 +465,7 @@ void launch_refine_orient(hipStream_t st, const Layout& L, const float* gpyr, co
 // SparseG4.
 void launch_g4_points(hipStream_t st, const Layout& L, const float* gpyr, const float* coef4, const Cand* pts, int n,
                       float* patch, int grid);
+// emit.hip.
 // half (sift_set_upsample: detection ran on the doubled image): every emitted
 // keypoint has x, y and size multiplied by 0.5f and the low byte of its octave
 // decremented (255 = octave -1) -- OpenCV's post-pass for firstOctave < 0.
@@ -494,7 +498,7 @@ struct DetMask {
 void launch_detmask(hipStream_t st, DetectBufs& D, int batch, const DetMask& dm, int rows, int cols, bool grid_form,
                     bool half = false);
 // Device status bits; bit i <-> sticky error word err[i] (DescArgs::err_flag = &err[0],
-// status_kernel).
+// emit.hip's status_kernel).
 constexpr int kErrAssert = 1;      // keypoint octave/layer outside the pyramid (CV_Assert)
 constexpr int kErrWorkspace = 2;   // candidate workspace overflow
 constexpr int kErrKpCapacity = 4;  // keypoint total above the output capacity

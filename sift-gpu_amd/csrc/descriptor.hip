@@ -9,7 +9,7 @@
 //    j-range is derived from the two slabs |r_rot|, |c_rot| < 2.5 (plus a
 //    margin), so about half of the (2r+1)^2 window is skipped; the exact float
 //    predicate of src/sift.cpp:620-621 still decides each sample.  Gradient
-//    magnitude / orientation per pixel come precomputed (detect.hip), so a
+//    magnitude / orientation per pixel come precomputed (extrema.hip), so a
 //    sample is one 8-byte gather + exp32f + the trilinear weights.
 //  * Accumulation by bin ownership: a sample's 8 corners (r0+dr, c0+dc, o0+do)
 //    always have 8 distinct parities (R&1, C&1, O&1).  Lane q of a group owns

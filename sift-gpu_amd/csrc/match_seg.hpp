@@ -10,6 +10,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "wave_scan.hpp"
 
 namespace sift {
 
@@ -132,34 +133,14 @@ __global__ __launch_bounds__(256) void knn_seg_merge_kernel(const P* __restrict_
 template <int kTile>
 __global__ __launch_bounds__(256) void seg_tiles_kernel(const int* __restrict__ qoff, int nseg, int q_cap,
                                                         int* __restrict__ tile_start) {
-  __shared__ int wsum[4];
-  __shared__ int carry_s;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  for (int b0 = 0; b0 < nseg; b0 += 256) {
-    const int b = b0 + threadIdx.x;
-    int n = 0;
-    if (b < nseg) {
-      const int s = clamp_row(qoff[b], q_cap), e = clamp_row(qoff[b + 1], q_cap);
-      n = e > s ? (e - s + kTile - 1) / kTile : 0;
-    }
-    int v = n;  // inclusive scan over the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int u = __shfl_up(v, d);
-      if (lane >= d) v += u;
-    }
-    if (lane == 63) wsum[wv] = v;
-    __syncthreads();
-    int base = carry_s;
-    for (int w = 0; w < wv; ++w) base += wsum[w];
-    if (b < nseg) tile_start[b] = base + v - n;
-    __syncthreads();
-    if (threadIdx.x == 255) carry_s = base + v;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) tile_start[nseg] = carry_s;
+  const int total = wg_scan_chunks<256>(
+      nseg,
+      [&](int b) {
+        const int s = clamp_row(qoff[b], q_cap), e = clamp_row(qoff[b + 1], q_cap);
+        return e > s ? (e - s + kTile - 1) / kTile : 0;
+      },
+      [&](int b, int x) { tile_start[b] = x; });
+  if (threadIdx.x == 0) tile_start[nseg] = total;
 }
 
 }  // namespace

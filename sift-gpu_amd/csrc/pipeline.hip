@@ -1,8 +1,9 @@
 // pipeline.hip -- the SIFT pipeline behind the C ABI (include/sift_hip.h) on
 // the context's one HIP stream: SIFT_NCL for a device batch and from host
 // memory, the six sub-module entry points, and the test helpers.  Host code
-// and one test kernel; the kernels live in blur.hip, pyramid_pc.hip,
-// detect.hip and descriptor.hip.
+// and one test kernel; the kernels live in blur.hip, pyramid_pc.hip, the
+// detection stages (extrema.hip, scan.hip, refine.hip, orient.hip, emit.hip)
+// and descriptor.hip.
 #include <limits.h>
 #include <math.h>
 #include <stdio.h>

@@ -30,6 +30,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "wave_scan.hpp"
 
 namespace sift {
 
@@ -58,11 +59,7 @@ __device__ __forceinline__ void select_digit(const int* hist, int want, SelShare
   }
   if (tid < kSelectBins) {  // waves 0..3, whole
     v = hist[kSelectBins - 1 - tid];
-    incl = v;
-    for (int off = 1; off < 64; off <<= 1) {
-      const int t = __shfl_up(incl, off);
-      if (lane >= off) incl += t;
-    }
+    incl = wave_scan_incl(v, lane);
     if (lane == 63) s.wsum[wv] = incl;
   }
   __syncthreads();

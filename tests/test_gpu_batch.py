@@ -166,6 +166,39 @@ def test_candidate_workspace_overflow_is_an_error(siftgpu, oracle):
         assert_bits_equal(desc1, g["desc"], "descriptors after recovery")
 
 
+def test_scan_forms_agree(siftgpu, oracle):
+    """launch_scan's two forms on one input: a two-image batch of the 160 x 128
+    synthetic image in a context whose candidate capacity is just at the switch
+    (2 x 32768 = kScanSmallMax slots: the one-workgroup scan, gather included)
+    and in one just above it (2 x 32769: reduce, tile scan, down-sweep and the
+    gather as its own launch).  Keypoints, offsets and descriptors byte-equal
+    between the two and equal to the CPU path's."""
+    import torch
+    B, r, c = 2, 160, 128
+    ref = [oracle.sift(oracle.synth_image(b, r, c)) for b in range(B)]
+    n = sum(len(k) for k, _ in ref)
+    assert n > 0
+    got = []
+    for per_image in (32768, 32769):
+        with siftgpu.Context(r, c, B, device=0) as ctx:
+            ctx.set_candidate_capacity(per_image)
+            imgs = torch.empty((B, r, c), dtype=torch.float32, device="cuda")
+            ctx.synth_images(imgs.data_ptr(), B, r, c, c, r * c, seed_base=0)
+            kpts = torch.full((n, 7), -1, dtype=torch.int32, device="cuda")
+            desc = torch.full((n, 128), -1.0, dtype=torch.float32, device="cuda")
+            offs = torch.full((B + 1,), -1, dtype=torch.int32, device="cuda")
+            ctx.detect_compute_batch(imgs.data_ptr(), B, r, c, c, r * c, kpts.data_ptr(), desc.data_ptr(), n,
+                                     offs.data_ptr())
+            ctx.sync()
+            got.append((offs.cpu().numpy(), kpts.cpu().numpy().view(np.uint8).reshape(n, 28), desc.cpu().numpy()))
+    for a, b, what in zip(got[0], got[1], ("offsets", "keypoints", "descriptors")):
+        assert_bits_equal(a, b, f"{what}: one-workgroup scan vs three-kernel scan")
+    o, k, d = got[0]
+    assert o.tolist() == np.concatenate([[0], np.cumsum([len(kr) for kr, _ in ref])]).tolist()
+    assert_bits_equal(k, np.concatenate([kp_bytes(kr) for kr, _ in ref]), "keypoints")
+    assert_bits_equal(d, np.concatenate([dr for _, dr in ref]), "descriptors")
+
+
 def test_batch_keypoint_capacity(siftgpu, oracle):
     """A batch call whose kp_cap is too small: sift_sync reports
     SIFT_E_CAPACITY, d_img_offsets[batch] holds the true total, and the

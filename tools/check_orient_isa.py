@@ -1,5 +1,5 @@
 """ISA check for the orientation histogram's ordered read-modify-write steps
-(detect.hip, orient_slots_kernel; reference src/sift.cpp:429-437: every bin
+(orient.hip, orient_slots_kernel; reference src/sift.cpp:429-437: every bin
 receives its terms in window raster order).
 
 Each batch of 8 samples is added by 8 steps; at step jj, lane jj of every
@@ -7,7 +7,7 @@ Each batch of 8 samples is added by 8 steps; at step jj, lane jj of every
 The order is held by an `asm volatile("; orient step jj")` memory barrier on
 an opaque copy of the lane index: without it hipcc rebuilt the eight guarded
 blocks as a switch on the lane index and ran them out of order (3 % of the
-angles a few ulps off).  This compiles detect.hip to gfx950
+angles a few ulps off).  This compiles orient.hip to gfx950
 assembly and checks, for every orient_slots_kernel instance, that
 
   * the markers appear in the sample loop as complete runs 0, 1, ..., 7;
@@ -31,10 +31,10 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, 'sift-gpu_amd', 'csrc', 'detect.hip')
+SRC = os.path.join(ROOT, 'sift-gpu_amd', 'csrc', 'orient.hip')
 
 
-def compile_asm(out='/tmp/detect_orient_check.s'):
+def compile_asm(out='/tmp/orient_check.s'):
     subprocess.check_call(['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off',
                            '-fno-slp-vectorize', '-I' + os.path.join(ROOT, 'include'),
                            '-I' + os.path.join(ROOT, 'sift-gpu_amd', 'build'), '--cuda-device-only', '-S', SRC,

@@ -890,6 +890,74 @@ int sift_find_homography_segmented(sift_ctx* ctx, const float* src_xy, const flo
 int sift_perspective_transform_segmented_device(sift_ctx* ctx, const double* d_H, const int* d_found, int n_segments,
                                                 const float* d_xy, int n_pts, float* d_out_xy);
 
+/* ---- affine and similarity transforms ---------------------------------------- */
+/* `estimateAffine2D` (SIFT_MODEL_AFFINE: rows (a b tx; c d ty), m = 3 model
+ * points) and `estimateAffinePartial2D` (SIFT_MODEL_SIMILARITY: rotation,
+ * uniform scale, translation, rows (a -b tx; b a ty), m = 2) by RANSAC, for
+ * consecutive frames where a homography's two spare parameters only fit noise.
+ * n point pairs as interleaved (x, y) floats; OpenCV's defaults are
+ * ransac_thresh 3, max_iters 2000, confidence 0.99.  A is a row-major 2x3;
+ * inlier_mask (n bytes, may be NULL) gets the RANSAC inliers.  Host code, no
+ * context.  SIFT_E_INVALID (A and the mask zeroed) when no model is found,
+ * n < m, max_iters < 1, confidence outside (0, 1) or model is unknown.
+ * The rule (csrc/affine_math.hpp) is sift_find_homography's loop with m in
+ * place of 4: n == m is a direct fit with no subset check and a mask of ones
+ * (none when the solve is singular: three collinear or two identical source
+ * points); otherwise subsets of m distinct rows from RNG(~0) -- affine: neither
+ * the three src nor the three dst points collinear; similarity: the two src
+ * points not identical --, a closed-form minimal solve in double (Cramer, or
+ * the complex quotient), a hypothesis wins iff it has more than
+ * max(best, m - 1) inliers, and max_iters shrinks after every win.  A pair is
+ * an inlier iff, with the six coefficients cast to float and unfused float
+ * arithmetic, (f0 x + f1 y + f2 - X)^2 + (f3 x + f4 y + f5 - Y)^2 <=
+ * (float)(thr * thr).  The final model is the ordinary least-squares fit to the
+ * best hypothesis's inliers (closed form over centred double sums in pair
+ * order): the residual is linear in the parameters, so this is the minimum
+ * OpenCV's refineIters = 10 LMSolver iterations look for, and there is no
+ * refineIters argument.  A singular or non-finite refit leaves the RANSAC model;
+ * the mask is the best hypothesis's, taken before the refit.
+ * The library's own rule, not bit-compatible with OpenCV: parity is pinned only
+ * against tests/affine_oracle.py, which restates the same steps.
+ * thr = -3 behaves as 3, thr = 0 admits only an exact zero error, and a thr
+ * whose square overflows float to +inf admits every pair with a finite or
+ * infinite (not NaN) error, so the first hypothesis ends the loop.
+ * Non-finite coordinates: the call terminates (every loop is bounded by a
+ * count), a hypothesis with a non-finite coefficient is no model, a row with a
+ * NaN coordinate is never an inlier, one with an infinite coordinate only under
+ * the +inf limit above; what the pair set as a whole gives (found, A) is
+ * otherwise unspecified, but A is always finite.  In the segmented forms below
+ * the other segments are unaffected. */
+#define SIFT_MODEL_AFFINE 0
+#define SIFT_MODEL_SIMILARITY 1
+int sift_estimate_affine(const float* src_xy, const float* dst_xy, int n, int model, double ransac_thresh,
+                         int max_iters, double confidence, double* A, unsigned char* inlier_mask);
+
+/* The same for every segment of a batch, on the device in stream order, with
+ * the contract of sift_find_homography_segmented_device: segment b's pairs are
+ * rows [clamp(m_offsets[b]), clamp(m_offsets[b+1])) of d_src_xy / d_dst_xy,
+ * clamped to m_cap, and each segment gets exactly what sift_estimate_affine
+ * gives for its pairs, bit for bit.  d_H is [n_segments][9] row-major: A's two
+ * rows, then 0 0 1, so sift_warp_perspective_segmented_device,
+ * sift_perspective_transform_segmented_device and the d_H / d_found prediction
+ * of sift_knn_match_window_segmented_device take it as it is.  d_found[b] is 1
+ * for a model, 0 for none, and then H[b] is nine zeros and the segment's mask
+ * bytes are 0.  max_iters < 1 or confidence outside (0, 1) gives every segment
+ * found = 0.  d_inlier_mask is [m_cap] bytes by pair row and may be NULL; bytes
+ * outside [clamp(m_offsets[0]), clamp(m_offsets[n_segments])) and rows of d_H /
+ * d_found past n_segments are never written.
+ * Enqueued on the context stream, no synchronisation, no scratch.  A NULL
+ * context, then an unknown model: SIFT_E_INVALID.  n_segments == 0 or m_cap ==
+ * 0: SIFT_OK, nothing enqueued.  A NULL required buffer: SIFT_E_INVALID
+ * (sift_last_error names it). */
+int sift_estimate_affine_segmented_device(sift_ctx* ctx, const float* d_src_xy, const float* d_dst_xy,
+                                          const int* d_m_offsets, int n_segments, int m_cap, int model,
+                                          double ransac_thresh, int max_iters, double confidence, double* d_H,
+                                          int* d_found, unsigned char* d_inlier_mask /* may be NULL */);
+/* Host buffers (synchronous); src_xy / dst_xy have m_cap rows: */
+int sift_estimate_affine_segmented(sift_ctx* ctx, const float* src_xy, const float* dst_xy, const int* m_offsets,
+                                   int n_segments, int m_cap, int model, double ransac_thresh, int max_iters,
+                                   double confidence, double* H, int* found, unsigned char* inlier_mask /* may be NULL */);
+
 /* ---- self-test ------------------------------------------------------------ */
 /* Evaluates one device arithmetic helper element-wise on host arrays (n
  * values), for bit-exact checks of the GPU math against the CPU oracle:

@@ -288,6 +288,14 @@ void launch_homography_seg(hipStream_t st, const float* src_xy, const float* dst
                            unsigned char* mask_out);
 void launch_perspective_seg(hipStream_t st, const double* H, const int* found, int n_segments, const float* xy,
                             int n_pts, float* out);
+// affine.hip: estimateAffine2D / estimateAffinePartial2D (RANSAC) on the host; A is 2x3 row-major.
+// model: SIFT_MODEL_AFFINE / SIFT_MODEL_SIMILARITY, anything else gives none.
+int estimate_affine_ransac(const float* src_xy, const float* dst_xy, int n, int model, double thr, int max_iters,
+                           double confidence, double* A, unsigned char* mask_out);
+// affine_batch.hip: the same per segment, one workgroup each, no scratch; H is [n_segments][9], last row 0 0 1.
+void launch_affine_seg(hipStream_t st, const float* src_xy, const float* dst_xy, const int* moff, int n_segments,
+                       int m_cap, int model, double thr, int max_iters, double confidence, double* H, int* found,
+                       unsigned char* mask_out);
 // sift_selftest_math ops 8 / 9: out[i] = update_num_iters(confidence, (good[i] of n[i] pairs), 4, 2000)
 void launch_update_num_iters_selftest(hipStream_t st, double confidence, const float* good, const float* n, float* out,
                                       int count);

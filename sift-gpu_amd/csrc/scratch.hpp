@@ -1,12 +1,12 @@
-// scratch.hpp -- how the matcher, byte-matcher, windowed-matcher, cross-check, front-end and segmented-homography entry
-// points divide the context's one scratch block (sift_ctx::d_match).  Each
+// scratch.hpp -- how the matcher, byte-matcher, windowed-matcher, cross-check, front-end, segmented-homography and
+// segmented-affine entry points divide the context's one scratch block (sift_ctx::d_match).  Each
 // layout is described once, as a function of a Carver, and run twice: on a null
 // base to measure the block, then on the block itself.  The three segmented
 // matchers share one host and one cross-match layout, templates over a metric
 // tag (L1F32, L1U8, L2SqrU8).  Plain host C++ (no HIP
 // include), so that tests/cpp/scratch_layout.cpp, match_u8_layout.cpp,
-// match_l2_u8_layout.cpp, cross_check_layout.cpp, homography_layout.cpp and match_window_layout.cpp check every
-// layout without a GPU.
+// match_l2_u8_layout.cpp, cross_check_layout.cpp, homography_layout.cpp, match_window_layout.cpp and
+// affine_layout.cpp check every layout without a GPU.
 #pragma once
 
 #include <math.h>
@@ -307,6 +307,23 @@ inline HomogHost homog_host_layout(Carver& a, int n_segments, int m_cap) {
   return {a.take<float>((size_t)m_cap * 2), a.take<float>((size_t)m_cap * 2), a.take<int>((size_t)n_segments + 1),
           a.take<double>((size_t)n_segments * 9), a.take<int>((size_t)n_segments),
           a.take<unsigned char>((size_t)m_cap), homog_layout(a, n_segments, m_cap)};
+}
+
+// ---- affine / similarity estimation (affine_batch.hip) ----
+// sift_estimate_affine_segmented_device: a round is kAffineRound hypotheses, one
+// per thread of the segment's workgroup.  A round's subsets and inlier counts
+// live in LDS, the hypotheses in registers, and the kernel's tail takes the
+// best hypothesis's mask again from its model, so the device form carves
+// nothing from the block.
+constexpr int kAffineRound = 128;
+
+// sift_estimate_affine_segmented: the staged point pairs and offsets, then the
+// staged results.
+struct AffineHost { float *src_xy, *dst_xy; int* m_off; double* H; int* found; unsigned char* mask; };
+inline AffineHost affine_host_layout(Carver& a, int n_segments, int m_cap) {
+  return {a.take<float>((size_t)m_cap * 2), a.take<float>((size_t)m_cap * 2), a.take<int>((size_t)n_segments + 1),
+          a.take<double>((size_t)n_segments * 9), a.take<int>((size_t)n_segments),
+          a.take<unsigned char>((size_t)m_cap)};
 }
 
 }  // namespace sift

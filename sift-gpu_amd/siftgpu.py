@@ -37,6 +37,9 @@ SIFT_E_WORKSPACE = -6  # internal candidate workspace overflow: an error, never 
 SIFT_FLAG_FAST, SIFT_FLAG_PROFILE, SIFT_FLAG_VERBOSE, SIFT_FLAG_NO_GRAPH = 0x1, 0x2, 0x4, 0x8
 N_SCALES, N_DOG, DESC_LEN = 5, 4, 128
 HOMOGRAPHY_ROUND = 64  # hypotheses per round of the segmented homography (scratch.hpp kHomogRound)
+AFFINE_ROUND = 128  # hypotheses per round of the segmented affine / similarity estimate (scratch.hpp kAffineRound)
+# sift_estimate_affine[_segmented[_device]]: the motion model
+SIFT_MODEL_AFFINE, SIFT_MODEL_SIMILARITY = 0, 1
 # sift_cross_match_segmented_device's metric: the distance and the type of the descriptor rows
 SIFT_METRIC_L1_F32, SIFT_METRIC_L1_U8, SIFT_METRIC_L2SQR_U8 = 0, 1, 2
 # sift_warp_perspective[_segmented_device]: the pixel type and the flag
@@ -160,6 +163,12 @@ def lib():
             "sift_find_homography_segmented": (ip, [vp, fp, fp, pint, ip, ip, ctypes.c_double, ip, ctypes.c_double,
                                                     ctypes.POINTER(ctypes.c_double), pint, vp]),
             "sift_perspective_transform_segmented_device": (ip, [vp, vp, vp, ip, vp, ip, vp]),
+            "sift_estimate_affine": (ip, [fp, fp, ip, ip, ctypes.c_double, ip, ctypes.c_double,
+                                          ctypes.POINTER(ctypes.c_double), vp]),
+            "sift_estimate_affine_segmented_device": (ip, [vp, vp, vp, vp, ip, ip, ip, ctypes.c_double, ip,
+                                                           ctypes.c_double, vp, vp, vp]),
+            "sift_estimate_affine_segmented": (ip, [vp, fp, fp, pint, ip, ip, ip, ctypes.c_double, ip,
+                                                    ctypes.c_double, ctypes.POINTER(ctypes.c_double), pint, vp]),
             "sift_multi_shard": (ip, [ip, ip, ip, pint, pint]),
             "sift_multi_merge_offsets": (ip, [ctypes.POINTER(pint), pint, ip, pint]),
             "sift_multi_create": (ip, [pint, ip, ip, ip, ip, ctypes.c_uint, ip, ip, ip, ctypes.POINTER(vp)]),
@@ -185,7 +194,8 @@ def lib():
                     "sift_multi_step_masked", "sift_compute_batch", "sift_compute",
                     "sift_knn_match_window_segmented_device", "sift_knn_match_window_segmented",
                     "sift_set_upsample", "sift_upsample2x", "sift_upsample2x_device",
-                    "sift_warp_perspective_segmented_device", "sift_warp_perspective"}  # absent from older builds (A/B runs against a saved library)
+                    "sift_warp_perspective_segmented_device", "sift_warp_perspective", "sift_estimate_affine",
+                    "sift_estimate_affine_segmented_device", "sift_estimate_affine_segmented"}  # absent from older builds (A/B runs against a saved library)
         for name, (res, args) in sigs.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -926,6 +936,49 @@ class Context:
         return [(H[b].reshape(3, 3).copy() if found[b] else None, mask[o[b]:max(o[b], o[b + 1])].copy())
                 for b in range(nseg)]
 
+    # ---- a whole batch: affine / similarity transform per segment of the same pairs ---
+    def estimate_affine_segmented_device(self, src_xy_ptr: int, dst_xy_ptr: int, m_offsets_ptr: int,
+                                         n_segments: int, m_cap: int, model: int, H_ptr: int, found_ptr: int,
+                                         mask_ptr: int | None = None, ransacReprojThreshold: float = 3.0,
+                                         maxIters: int = 2000, confidence: float = 0.99):
+        """Device-pointer form (no sync) of estimateAffine2D (model SIFT_MODEL_AFFINE)
+        or estimateAffinePartial2D (SIFT_MODEL_SIMILARITY) for every segment
+        [m_offsets[b], m_offsets[b+1]) of ratio_matches_device's point pairs:
+        H_ptr [n_segments][9] float64 with the last row 0 0 1 (what the warp, the
+        corner transform and the windowed matcher take), found_ptr [n_segments]
+        int32, mask_ptr [m_cap] uint8 or None."""
+        vp = lambda p: ctypes.c_void_p(p or None)  # noqa: E731
+        self._check("sift_estimate_affine_segmented_device",
+                    self._L.sift_estimate_affine_segmented_device(
+                        self.h, vp(src_xy_ptr), vp(dst_xy_ptr), vp(m_offsets_ptr), n_segments, m_cap, int(model),
+                        float(ransacReprojThreshold), int(maxIters), float(confidence), vp(H_ptr), vp(found_ptr),
+                        vp(mask_ptr)))
+
+    def estimateAffineBatch(self, src, dst, m_offsets, model: int, ransacReprojThreshold: float = 3.0,
+                            maxIters: int = 2000, confidence: float = 0.99):
+        """estimateAffine2D / estimateAffinePartial2D for every segment at once
+        (host arrays): a list of (A 2x3 float64 or None, inlier mask
+        uint8[segment's pairs]) per segment, offsets clamped to the number of pairs."""
+        s = np.ascontiguousarray(src, np.float32).reshape(-1, 2)
+        d = np.ascontiguousarray(dst, np.float32).reshape(-1, 2)
+        mo = np.ascontiguousarray(m_offsets, np.int32)
+        if len(s) != len(d) or mo.ndim != 1 or len(mo) < 1:
+            raise ValueError("src / dst must be [n, 2] and m_offsets n_segments + 1 entries")
+        nseg, n = len(mo) - 1, len(s)
+        H = np.zeros((nseg, 9), np.float64)
+        found = np.zeros(nseg, np.int32)
+        mask = np.zeros(n, np.uint8)
+        pint = ctypes.POINTER(ctypes.c_int)
+        self._check("sift_estimate_affine_segmented",
+                    self._L.sift_estimate_affine_segmented(
+                        self.h, _fp(s), _fp(d), mo.ctypes.data_as(pint), nseg, n, int(model),
+                        float(ransacReprojThreshold), int(maxIters), float(confidence),
+                        H.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), found.ctypes.data_as(pint),
+                        mask.ctypes.data))
+        o = np.clip(mo.astype(np.int64), 0, n)
+        return [(H[b, :6].reshape(2, 3).copy() if found[b] else None, mask[o[b]:max(o[b], o[b + 1])].copy())
+                for b in range(nseg)]
+
     # ---- device batch API ------------------------------------------------
     def synth_images(self, out_ptr: int, batch: int, rows: int, cols: int, row_stride: int,
                      img_stride: int, seed_base: int = 0):
@@ -1364,6 +1417,35 @@ def perspectiveTransform(points, H):
     if rc != SIFT_OK:
         raise SiftError("sift_perspective_transform", rc, "bad argument")
     return out
+
+
+def _estimate_affine(model, from_, to, ransacReprojThreshold, maxIters, confidence):
+    src = np.ascontiguousarray(from_, np.float32).reshape(-1, 2)
+    dst = np.ascontiguousarray(to, np.float32).reshape(-1, 2)
+    if len(src) != len(dst):
+        raise ValueError("point counts differ")
+    A = np.zeros(6, np.float64)
+    m = np.zeros(max(len(src), 1), np.uint8)
+    rc = lib().sift_estimate_affine(_fp(src), _fp(dst), len(src), model, float(ransacReprojThreshold), int(maxIters),
+                                    float(confidence), A.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                    m.ctypes.data)
+    if rc != SIFT_OK:
+        return None, np.zeros(len(src), np.uint8)
+    return A.reshape(2, 3), m[:len(src)]
+
+
+def estimateAffine2D(from_, to, ransacReprojThreshold: float = 3.0, maxIters: int = 2000, confidence: float = 0.99):
+    """cv::estimateAffine2D(from, to, RANSAC) -> (A 2x3 float64 or None, inlier mask).  Host code in
+    the library (affine.hip); the final model is the least-squares fit to the inliers, the minimum
+    OpenCV's refineIters look for (include/sift_hip.h), so there is no refineIters argument."""
+    return _estimate_affine(SIFT_MODEL_AFFINE, from_, to, ransacReprojThreshold, maxIters, confidence)
+
+
+def estimateAffinePartial2D(from_, to, ransacReprojThreshold: float = 3.0, maxIters: int = 2000,
+                            confidence: float = 0.99):
+    """cv::estimateAffinePartial2D(from, to, RANSAC): rotation, uniform scale and translation,
+    A = (a -b tx; b a ty) -> (A 2x3 float64 or None, inlier mask)."""
+    return _estimate_affine(SIFT_MODEL_SIMILARITY, from_, to, ransacReprojThreshold, maxIters, confidence)
 
 
 WARP_INVERSE_MAP = 16  # cv::WARP_INVERSE_MAP

@@ -667,6 +667,61 @@ int sift_knn_match_l2sqr_u8_segmented(sift_ctx* ctx, const uint8_t* query, const
 int sift_knn_match_l2sqr_u8(sift_ctx* ctx, const uint8_t* query, int n_query, const uint8_t* train, int n_train,
                             int k, int* idx, float* dist);
 
+/* ---- squared L2 on float descriptors (opt-in; match_l2_f32.hip) --------------- */
+/* sift_knn_match_l1_segmented_device with the squared Euclidean distance on the
+ * float rows themselves (cv::BFMatcher's default NORM_L2 on SIFT descriptors,
+ * less the square root), formed on the exact f32 matrix pipe by one rule that a
+ * CPU restates bit for bit.  pi is one fixed permutation of 0..127, the same
+ * for every call and shape (the order the 16-byte operand loads give):
+ *   pi = 0 4 1 5 2 6 3 7,  8 12 9 13 10 14 11 15,  ...,
+ *        120 124 121 125 122 126 123 127
+ * i.e. pi[8 c + 2 j + h] = 8 c + 4 h + j for c < 16, j < 4, h < 2.  With
+ *   chain(x, y) = fmaf(x[pi127], y[pi127], ... fmaf(x[pi0], y[pi0], 0.0f))
+ * (one rounding per product, IEEE binary32, round to nearest even):
+ *   dot = chain(q, t), nq = chain(q, q), nt = chain(t, t),
+ *   s = nq + nt                      (one rounding),
+ *   d = fmaf(-2.0f, dot, s),
+ *   d = d < 0 ? 0 : d                (a comparison: NaN stays NaN).
+ * d_dist holds d, the SQUARED distance (cv::NORM_L2SQR); no square root is
+ * taken on the device, and the order of neighbours is NORM_L2's.  The ratio
+ * test on it is sift_ratio_matches[_device] unchanged with ratio * ratio passed
+ * as its ratio (0.86 * 0.86 for the application's 0.86); cross-check is two
+ * calls, the second with the sides exchanged and k = 1, into
+ * sift_cross_check_matches_device.  No host value is read in between.
+ * Accuracy: the form nq + nt - 2 dot cancels, so against the real-number
+ * sum (q[e] - t[e])^2 the absolute error is about 2 gamma_130 (nq + nt),
+ * gamma_n = n 2^-24 / (1 - n 2^-24): about 1.6e-5 (nq + nt), whatever d is --
+ * two nearly equal rows get a distance near 0 with that absolute, not
+ * relative, error.  The exact-difference form does not map to the matrix pipe.
+ * Denormal values are not flushed.  Every (q, t) distance is formed in one
+ * tile over all 128 elements, so no capacity, offset, split or tile position
+ * changes a value.
+ * Order, tie rule (an earlier train index first at equal distance), local
+ * indices, clamps and the -1 / +inf fill are sift_knn_match_l1_segmented's word
+ * for word: a train row at d = +inf is never a neighbour; where fewer than k
+ * train rows are at a finite distance the missing entries are idx -1, dist
+ * +inf.  Descriptors with NaN or infinite elements are unspecified.  Which rows
+ * are touched is that contract too: d_idx / d_dist are [q_cap][k]; rows before
+ * q_offsets[0] and rows at or past min(q_offsets[n_segments], q_cap) are left
+ * untouched; every bound is clamped to q_cap / t_cap; d_t_offsets == NULL is a
+ * shared train set; n_segments == 0 or q_cap == 0: SIFT_OK, nothing enqueued; a
+ * NULL context or required buffer: SIFT_E_INVALID.  Rows 16-byte aligned.
+ * Enqueued on the context stream with no synchronisation (the scratch, sized
+ * from the capacities, grows, with a wait, only when a call needs more than any
+ * call before it).  Consecutive frames: d_train = d_query, d_t_offsets =
+ * d_q_offsets + 1. */
+int sift_knn_match_l2sqr_f32_segmented_device(sift_ctx* ctx, const float* d_query, const int* d_q_offsets,
+                                              int n_segments, int q_cap, const float* d_train,
+                                              const int* d_t_offsets /* NULL = shared */, int t_cap, int k,
+                                              int* d_idx, float* d_dist);
+/* Host buffers (synchronous); query has q_cap rows, train t_cap rows: */
+int sift_knn_match_l2sqr_f32_segmented(sift_ctx* ctx, const float* query, const int* q_offsets, int n_segments,
+                                       int q_cap, const float* train, const int* t_offsets /* NULL = shared */,
+                                       int t_cap, int k, int* idx, float* dist);
+/* Host buffers (synchronous): one segment of n_query rows over all n_train rows. */
+int sift_knn_match_l2sqr_f32(sift_ctx* ctx, const float* query, int n_query, const float* train, int n_train,
+                             int k, int* idx, float* dist);
+
 /* One kept match: cv::DMatch's queryIdx / trainIdx (local to their segments),
  * distance, and the segment in imgIdx's place.  16 bytes. */
 typedef struct sift_match {
@@ -757,6 +812,12 @@ int sift_cross_check_matches(sift_ctx* ctx, const int* idx, const float* dist, i
 #define SIFT_METRIC_L1_F32 0
 #define SIFT_METRIC_L1_U8 1
 #define SIFT_METRIC_L2SQR_U8 2
+/* Float rows under squared L2 (sift_knn_match_l2sqr_f32_segmented_device): a
+ * name for documentation and the Python module.  The one-call cross-match and
+ * the windowed matcher take the three metrics above only and reject this one
+ * (SIFT_E_INVALID); cross-check with it is two matcher calls and
+ * sift_cross_check_matches_device. */
+#define SIFT_METRIC_L2SQR_F32 3
 /* The whole job in one call: the forward pass of the metric's segmented matcher
  * (k = 2 when ratio > 0, else k = 1), the reverse pass (k = 1, the sides
  * exchanged -- derived from these arguments) and the stage above, all enqueued

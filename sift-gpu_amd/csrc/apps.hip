@@ -1,15 +1,15 @@
 // apps.hip -- the application stages behind the C ABI (include/sift_hip.h):
-// the L1 kNN matcher, the byte quantiser, the three segmented matchers (float
-// L1, byte L1, byte squared L2), the windowed matcher, the ratio test with
+// the L1 kNN matcher, the byte quantiser, the four segmented matchers (float
+// L1, byte L1, byte squared L2, float squared L2), the windowed matcher, the ratio test with
 // point pairs, the cross-check stage with its one-call form, the BGR8 front
 // end and the doubled image, each in a device and a host form, the one-pair
 // homography wrappers, the segmented homography and corner transform, the
 // affine / similarity estimate (one pair set and segmented), and the
 // perspective warp of a batch.  Host code only; the kernels live in match.hip,
-// match_u8.hip, match_l2_u8.hip, match_window.hip, cross_check.hip,
+// match_u8.hip, match_l2_u8.hip, match_l2_f32.hip, match_window.hip, cross_check.hip,
 // frontend.hip, upsample.hip, homography_batch.hip, affine_batch.hip and warp.hip (the one-pair
 // homography and affine estimate are host code in homography.hip and affine.hip).  The segmented matchers are one path, written once as
-// function templates over a metric tag (MatchL1F32, MatchL1U8, MatchL2SqrU8);
+// function templates over a metric tag (MatchL1F32, MatchL1U8, MatchL2SqrU8, MatchL2SqrF32);
 // their extern "C" entry points only forward.  Every form carves its scratch
 // from the context's one block by a layout of scratch.hpp.
 #include <cstring>
@@ -23,7 +23,7 @@ using namespace sift;
 namespace {
 
 static_assert(kDescRow == kDescLen && sizeof(Float2) == sizeof(float2) && sizeof(Int2) == sizeof(int2) &&
-                  kL2PadRows == kL2NormPad,
+                  kL2PadRows == kL2NormPad && kL2F32PadRows == kL2F32NormPad,
               "scratch.hpp restates these without the HIP headers");
 float2* dev(Float2* p) { return reinterpret_cast<float2*>(p); }
 int2* dev(Int2* p) { return reinterpret_cast<int2*>(p); }
@@ -131,7 +131,7 @@ int check_seg(sift_ctx* c, const void* query, const int* q_offsets, int n_segmen
   return SIFT_OK;
 }
 
-// ---- the three segmented matchers: one metric description, one path ----
+// ---- the four segmented matchers: one metric description, one path ----
 // One segmented call: the buffers are device pointers.
 template <typename Row>
 struct SegCall {
@@ -140,7 +140,8 @@ struct SegCall {
 };
 
 // A metric: scratch.hpp's row type and device pieces, and here the stage, the
-// split count and the launcher (match.hip, match_u8.hip, match_l2_u8.hip).
+// split count and the launcher (match.hip, match_u8.hip, match_l2_u8.hip,
+// match_l2_f32.hip).
 struct MatchL1F32 : L1F32 {
   static constexpr int kStage = ST_MATCH_SEG;
   static constexpr auto splits = knn_seg_splits;
@@ -163,6 +164,14 @@ struct MatchL2SqrU8 : L2SqrU8 {
   static void launch(hipStream_t st, const SegCall<Row>& A, const Seg& s) {
     launch_knn_l2sqr_u8_seg(st, A.q, A.qoff, A.n_segments, A.q_cap, A.t, A.toff, A.t_cap, A.k, A.splits, s.tile_start,
                             s.q_norm, s.t_norm, dev(s.parts.dist), dev(s.parts.idx), A.idx, A.dist);
+  }
+};
+struct MatchL2SqrF32 : L2SqrF32 {
+  static constexpr int kStage = ST_MATCH_L2_F32;
+  static constexpr auto splits = knn_l2_f32_seg_splits;
+  static void launch(hipStream_t st, const SegCall<Row>& A, const Seg& s) {
+    launch_knn_l2sqr_f32_seg(st, A.q, A.qoff, A.n_segments, A.q_cap, A.t, A.toff, A.t_cap, A.k, A.splits, s.tile_start,
+                             s.q_norm, s.t_norm, dev(s.parts.dist), dev(s.parts.idx), A.idx, A.dist);
   }
 };
 
@@ -228,7 +237,7 @@ int seg_match_host(sift_ctx* c, const Row* query, const int* q_offsets, int n_se
   return seg_host<M>(c, query, q_offsets, n_segments, q_cap, train, t_offsets, t_cap, k, idx, dist);
 }
 
-// The one-segment byte entry points.
+// The one-segment entry points (the byte metrics and float squared L2).
 template <typename M, typename Row = typename M::Row>
 int one_seg_match_host(sift_ctx* c, const Row* query, int n_query, const Row* train, int n_train, int k, int* idx,
                        float* dist) {
@@ -566,6 +575,25 @@ int sift_knn_match_l2sqr_u8_segmented(sift_ctx* c, const uint8_t* query, const i
 int sift_knn_match_l2sqr_u8(sift_ctx* c, const uint8_t* query, int n_query, const uint8_t* train, int n_train, int k,
                             int* idx, float* dist) {
   return one_seg_match_host<MatchL2SqrU8>(c, query, n_query, train, n_train, k, idx, dist);
+}
+
+int sift_knn_match_l2sqr_f32_segmented_device(sift_ctx* c, const float* d_query, const int* d_q_offsets,
+                                              int n_segments, int q_cap, const float* d_train,
+                                              const int* d_t_offsets, int t_cap, int k, int* d_idx, float* d_dist) {
+  return seg_match_device<MatchL2SqrF32>(c, d_query, d_q_offsets, n_segments, q_cap, d_train, d_t_offsets, t_cap, k,
+                                         d_idx, d_dist);
+}
+
+int sift_knn_match_l2sqr_f32_segmented(sift_ctx* c, const float* query, const int* q_offsets, int n_segments,
+                                       int q_cap, const float* train, const int* t_offsets, int t_cap, int k,
+                                       int* idx, float* dist) {
+  return seg_match_host<MatchL2SqrF32>(c, query, q_offsets, n_segments, q_cap, train, t_offsets, t_cap, k, idx, dist);
+}
+
+// One segment [0, n_query) over the shared train set; the library writes the two offsets itself.
+int sift_knn_match_l2sqr_f32(sift_ctx* c, const float* query, int n_query, const float* train, int n_train, int k,
+                             int* idx, float* dist) {
+  return one_seg_match_host<MatchL2SqrF32>(c, query, n_query, train, n_train, k, idx, dist);
 }
 
 int sift_ratio_matches_device(sift_ctx* c, const int* d_idx, const float* d_dist, const int* d_q_offsets,

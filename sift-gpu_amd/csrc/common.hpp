@@ -335,6 +335,17 @@ int knn_l2_u8_seg_splits(int q_cap, int n_segments, int t_cap, bool seg_train);
 void launch_knn_l2sqr_u8_seg(hipStream_t st, const uint8_t* q, const int* qoff, int n_segments, int q_cap,
                              const uint8_t* t, const int* toff, int t_cap, int k, int splits, int* tile_start,
                              int* q_norm, int* t_norm, int2* part_d, int2* part_i, int* idx, float* dist);
+// match_l2_f32.hip: the segmented squared-L2 matcher on float rows (f32 MFMA) --
+// the grid is knn_l2_f32_seg_max_tiles() query tiles by knn_l2_f32_seg_splits()
+// train splits; tile_start is [n_segments + 1] ints of scratch, q_norm [q_cap]
+// and t_norm [t_cap + kL2F32NormPad] floats (written by the launch's own
+// pre-kernel), the float partials [splits * q_cap] (unused when splits == 1).
+constexpr int kL2F32NormPad = 64;
+int knn_l2_f32_seg_max_tiles(int q_cap, int n_segments);
+int knn_l2_f32_seg_splits(int q_cap, int n_segments, int t_cap, bool seg_train);
+void launch_knn_l2sqr_f32_seg(hipStream_t st, const float* q, const int* qoff, int n_segments, int q_cap,
+                              const float* t, const int* toff, int t_cap, int k, int splits, int* tile_start,
+                              float* q_norm, float* t_norm, float2* part_d, int2* part_i, int* idx, float* dist);
 // Ratio test + ordered compaction + point gather; blk_scan is
 // [ratio_blocks(q_cap) + 1] ints of scratch.
 int ratio_blocks(int q_cap);

@@ -1,11 +1,11 @@
 // scratch.hpp -- how the matcher, byte-matcher, windowed-matcher, cross-check, front-end, segmented-homography and
 // segmented-affine entry points divide the context's one scratch block (sift_ctx::d_match).  Each
 // layout is described once, as a function of a Carver, and run twice: on a null
-// base to measure the block, then on the block itself.  The three segmented
+// base to measure the block, then on the block itself.  The four segmented
 // matchers share one host and one cross-match layout, templates over a metric
-// tag (L1F32, L1U8, L2SqrU8).  Plain host C++ (no HIP
+// tag (L1F32, L1U8, L2SqrU8, L2SqrF32).  Plain host C++ (no HIP
 // include), so that tests/cpp/scratch_layout.cpp, match_u8_layout.cpp,
-// match_l2_u8_layout.cpp, cross_check_layout.cpp, homography_layout.cpp, match_window_layout.cpp and
+// match_l2_u8_layout.cpp, match_l2_f32_layout.cpp, cross_check_layout.cpp, homography_layout.cpp, match_window_layout.cpp and
 // affine_layout.cpp check every layout without a GPU.
 #pragma once
 
@@ -107,7 +107,20 @@ inline SegPartsL2U8 seg_l2_u8_layout(Carver& a, int n_segments, int q_cap, int t
           {a.take<Int2>(n), a.take<Int2>(n)}};
 }
 
-// ---- one description of the three segmented matchers' scratch ----
+// ---- squared L2 on float descriptors (match_l2_f32.hip) ----
+// sift_knn_match_l2sqr_f32_segmented_device: the query-tile table, one float per
+// row for chain(x, x) -- every query row, every train row and kL2F32PadRows
+// entries after them, which a step at the end of the train buffer reads and
+// masks -- then the float partials of knn_l2_f32_seg_splits() splits (none for
+// one split).
+constexpr int kL2F32PadRows = 64;  // common.hpp's kL2F32NormPad
+struct SegPartsL2F32 { int* tile_start; float *q_norm, *t_norm; KnnParts parts; };
+inline SegPartsL2F32 seg_l2_f32_layout(Carver& a, int n_segments, int q_cap, int t_cap, int splits) {
+  return {a.take<int>((size_t)n_segments + 1), a.take<float>((size_t)q_cap),
+          a.take<float>((size_t)t_cap + kL2F32PadRows), knn_parts(a, splits > 1 ? (size_t)splits * q_cap : 0)};
+}
+
+// ---- one description of the four segmented matchers' scratch ----
 // What a layout needs of a metric: the element type of a descriptor row and the
 // device form's pieces (the L1 forms ignore t_cap).  apps.hip adds the stage,
 // the split count and the launcher to each.
@@ -123,9 +136,13 @@ struct L2SqrU8 {
   using Row = uint8_t; using Seg = SegPartsL2U8;
   static Seg layout(Carver& a, int n, int q_cap, int t_cap, int s) { return seg_l2_u8_layout(a, n, q_cap, t_cap, s); }
 };
+struct L2SqrF32 {
+  using Row = float; using Seg = SegPartsL2F32;
+  static Seg layout(Carver& a, int n, int q_cap, int t_cap, int s) { return seg_l2_f32_layout(a, n, q_cap, t_cap, s); }
+};
 
 // The host form of a segmented matcher, and the one-segment byte forms
-// (sift_knn_match_l1_u8, _l2sqr_u8: one segment over a shared train set, the
+// (sift_knn_match_l1_u8, _l2sqr_u8, _l2sqr_f32: one segment over a shared train set, the
 // library writes q_off itself): the staged rows, results and offsets -- t_off
 // keeps its place when the caller has no train offsets, and is null then --
 // then the device form's pieces.
@@ -142,9 +159,11 @@ SegHostOf<M> seg_host_layout_of(Carver& a, int n_segments, int q_cap, int t_cap,
 using SegHost = SegHostOf<L1F32>;  // the names the layout tests use
 using SegHostU8 = SegHostOf<L1U8>;
 using SegHostL2U8 = SegHostOf<L2SqrU8>;
+using SegHostL2F32 = SegHostOf<L2SqrF32>;
 constexpr auto seg_host_layout = seg_host_layout_of<L1F32>;
 constexpr auto seg_u8_host_layout = seg_host_layout_of<L1U8>;
 constexpr auto seg_l2_u8_host_layout = seg_host_layout_of<L2SqrU8>;
+constexpr auto seg_l2_f32_host_layout = seg_host_layout_of<L2SqrF32>;
 
 // sift_descriptors_to_u8: the staged float rows, then the byte rows.
 struct QuantHostU8 { float* desc; uint8_t* out; };

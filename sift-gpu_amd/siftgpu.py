@@ -42,6 +42,7 @@ AFFINE_ROUND = 128  # hypotheses per round of the segmented affine / similarity 
 SIFT_MODEL_AFFINE, SIFT_MODEL_SIMILARITY = 0, 1
 # sift_cross_match_segmented_device's metric: the distance and the type of the descriptor rows
 SIFT_METRIC_L1_F32, SIFT_METRIC_L1_U8, SIFT_METRIC_L2SQR_U8 = 0, 1, 2
+SIFT_METRIC_L2SQR_F32 = 3  # a name only: the one-call cross-match and the windowed matcher reject it
 # sift_warp_perspective[_segmented_device]: the pixel type and the flag
 SIFT_PIXEL_F32, SIFT_PIXEL_U8 = 0, 1
 SIFT_WARP_INVERSE_MAP = 0x1
@@ -144,6 +145,9 @@ def lib():
             "sift_knn_match_l2sqr_u8_segmented_device": (ip, [vp, vp, vp, ip, ip, vp, vp, ip, ip, vp, vp]),
             "sift_knn_match_l2sqr_u8_segmented": (ip, [vp, vp, pint, ip, ip, vp, pint, ip, ip, pint, fp]),
             "sift_knn_match_l2sqr_u8": (ip, [vp, vp, ip, vp, ip, ip, pint, fp]),
+            "sift_knn_match_l2sqr_f32_segmented_device": (ip, [vp, vp, vp, ip, ip, vp, vp, ip, ip, vp, vp]),
+            "sift_knn_match_l2sqr_f32_segmented": (ip, [vp, fp, pint, ip, ip, fp, pint, ip, ip, pint, fp]),
+            "sift_knn_match_l2sqr_f32": (ip, [vp, fp, ip, fp, ip, ip, pint, fp]),
             "sift_ratio_matches_device": (ip, [vp, vp, vp, vp, ip, ip, ctypes.c_double, vp, vp, vp, vp, vp, vp, ip,
                                                vp]),
             "sift_ratio_matches": (ip, [vp, pint, fp, pint, ip, ip, ctypes.c_double, vp, vp, ip, pint, vp, fp, fp,
@@ -745,6 +749,41 @@ class Context:
         are fewer than k train rows."""
         return self._one_seg_u8("sift_knn_match_l2sqr_u8", query, train, k)
 
+    # ---- squared L2 on float descriptors (f32 MFMA; opt-in) --------------------
+    def knn_match_l2sqr_f32_segmented_device(self, query_ptr: int, q_offsets_ptr: int, n_segments: int, q_cap: int,
+                                             train_ptr: int, t_offsets_ptr: int | None, t_cap: int, k: int,
+                                             idx_ptr: int, dist_ptr: int):
+        """knn_match_segmented_device with the squared L2 distance on the float
+        rows (no sync): same arguments and contract; dist is the squared distance
+        by the rule of sift_hip.h (a fixed-order fmaf chain, d = nq + nt - 2 dot
+        clamped at 0).  No square root is taken: pass ratio * ratio to
+        ratio_matches_device (0.86 ** 2 for the usual 0.86).  Cross-check: a second
+        call with the sides exchanged and k = 1, then cross_check_matches_device."""
+        self._seg_device("sift_knn_match_l2sqr_f32_segmented_device", query_ptr, q_offsets_ptr, n_segments, q_cap,
+                         train_ptr, t_offsets_ptr, t_cap, k, idx_ptr, dist_ptr)
+
+    @staticmethod
+    def _f32_rows(a):
+        return np.ascontiguousarray(a, np.float32).reshape(-1, DESC_LEN)
+
+    def knnMatchL2SqrF32Segmented(self, query: np.ndarray, q_offsets, train: np.ndarray, t_offsets=None, k: int = 2):
+        """knnMatchSegmented with the squared L2 distance (host arrays): idx int32,
+        dist float32 (squared) [len(query), k]."""
+        return self._seg_host("sift_knn_match_l2sqr_f32_segmented", self._f32_rows(query), q_offsets,
+                              self._f32_rows(train), t_offsets, k)
+
+    def knnMatchL2SqrF32(self, query: np.ndarray, train: np.ndarray, k: int = 2):
+        """knnMatch with the squared L2 distance on float descriptors: idx int32,
+        dist float32 (squared) [n_query, k]; idx -1 / dist +inf where there are
+        fewer than k train rows."""
+        q, t = self._f32_rows(query), self._f32_rows(train)
+        idx = np.empty((len(q), k), np.int32)
+        dist = np.empty((len(q), k), np.float32)
+        self._check("sift_knn_match_l2sqr_f32",
+                    self._L.sift_knn_match_l2sqr_f32(self.h, _fp(q), len(q), _fp(t), len(t), k,
+                                                     idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _fp(dist)))
+        return idx, dist
+
     # ---- matching within a search window (spatially gated kNN) for a whole batch ----
     def knn_match_window_segmented_device(self, metric: int, query_ptr: int, q_kpts_ptr: int, q_offsets_ptr: int,
                                           n_segments: int, q_cap: int, train_ptr: int, t_kpts_ptr: int,
@@ -1300,7 +1339,8 @@ class BFMatcher:
     arrays take the byte matcher (integer distances).  NORM_L2SQR: two uint8
     arrays only, DMatch.distance is the squared distance (for a ratio test use
     ratio_test(matches, ratio ** 2)).  NORM_L2 (the square root) is not
-    implemented.  crossCheck=True raises: the mutual-nearest-neighbour filter is
+    implemented here: Euclidean matching of float descriptors is the module
+    function l2_match(query, train, k, squared).  crossCheck=True raises: the mutual-nearest-neighbour filter is
     the module function cross_check_match(query, train, normType)."""
 
     def __init__(self, normType: int = NORM_L1, crossCheck: bool = False, ctx: Context | None = None):
@@ -1329,7 +1369,8 @@ def cross_check_match(query, train, normType: int = NORM_L1, ctx: Context | None
     of descriptor sets: the list of DMatch (q, t) where t is q's nearest train row
     and q is t's nearest query row, in query order; the lower index wins at equal
     distance in both directions.  The matcher is picked from the dtypes as
-    BFMatcher.knnMatch picks it (NORM_L2SQR: two uint8 arrays, squared distances).
+    BFMatcher.knnMatch picks it (NORM_L2SQR: two uint8 arrays, squared distances;
+    for float descriptors under L2 see l2_match and Context.knnMatchL2SqrF32Segmented).
     Two matcher passes and the cross-check stage (Context.crossCheckMatches)."""
     both_u8 = np.asarray(query).dtype == np.uint8 and np.asarray(train).dtype == np.uint8
     if normType not in (NORM_L1, NORM_L2SQR):
@@ -1356,7 +1397,8 @@ def window_match(query_desc, query_kpts, train_desc, train_kpts, radius, H=None,
     it.  Per query a list of up to k DMatch, nearest first.  The matcher is picked
     from the dtypes as BFMatcher.knnMatch picks it.  image_size = (rows, cols) of
     the train image only shapes the search grid (default: the extent of the train
-    keypoints); no result depends on it."""
+    keypoints); no result depends on it.  Float descriptors under L2 have no
+    windowed form; l2_match is their dense matcher."""
     both_u8 = np.asarray(query_desc).dtype == np.uint8 and np.asarray(train_desc).dtype == np.uint8
     if normType not in (NORM_L1, NORM_L2SQR):
         raise ValueError("only NORM_L1 and NORM_L2SQR are implemented")
@@ -1373,6 +1415,22 @@ def window_match(query_desc, query_kpts, train_desc, train_kpts, radius, H=None,
     idx, dist = ctx.knnMatchWindowSegmented(metric, q, query_kpts, [0, len(q)], t, tk, None, radius,
                                             None if H is None else np.asarray(H, np.float64).reshape(1, 9), None,
                                             image_size, k)
+    return [[DMatch(i, int(idx[i, j]), 0, float(dist[i, j])) for j in range(k) if idx[i, j] >= 0]
+            for i in range(len(idx))]
+
+
+def l2_match(query, train, k: int = 2, squared: bool = False, ctx: Context | None = None):
+    """`cv::BFMatcher(NORM_L2).knnMatch(query, train, k)` on float descriptors
+    (squared=True: NORM_L2SQR): per query a list of up to k DMatch, nearest first,
+    the lower train index first at equal distance.  The device forms the squared
+    distance by the fixed rule of sift_hip.h (Context.knnMatchL2SqrF32);
+    squared=False takes np.sqrt of those float32 values on the host, which is
+    correctly rounded.  A ratio test on squared distances is
+    ratio_test(matches, ratio ** 2)."""
+    ctx = ctx or _ctx(1, 1)
+    idx, dist = ctx.knnMatchL2SqrF32(query, train, k)
+    if not squared:
+        dist = np.sqrt(dist)
     return [[DMatch(i, int(idx[i, j]), 0, float(dist[i, j])) for j in range(k) if idx[i, j] >= 0]
             for i in range(len(idx))]
 

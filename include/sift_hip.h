@@ -700,8 +700,13 @@ int sift_knn_match_l2sqr_u8(sift_ctx* ctx, const uint8_t* query, int n_query, co
  * indices, clamps and the -1 / +inf fill are sift_knn_match_l1_segmented's word
  * for word: a train row at d = +inf is never a neighbour; where fewer than k
  * train rows are at a finite distance the missing entries are idx -1, dist
- * +inf.  Descriptors with NaN or infinite elements are unspecified.  Which rows
- * are touched is that contract too: d_idx / d_dist are [q_cap][k]; rows before
+ * +inf.  Finite elements can give d = +inf (s overflows) or d = NaN (nq or nt
+ * and dot both overflow: inf - inf); a row at a NaN d is never a neighbour
+ * either, exactly like one at +inf, because the order is a strict '<', which is
+ * false on NaN: its place is filled as above, idx -1 / dist +inf, so no NaN
+ * ever appears in d_dist.  Descriptors with NaN or infinite elements are
+ * unspecified.
+ * Which rows are touched is that contract too: d_idx / d_dist are [q_cap][k]; rows before
  * q_offsets[0] and rows at or past min(q_offsets[n_segments], q_cap) are left
  * untouched; every bound is clamped to q_cap / t_cap; d_t_offsets == NULL is a
  * shared train set; n_segments == 0 or q_cap == 0: SIFT_OK, nothing enqueued; a

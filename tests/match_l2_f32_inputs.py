@@ -6,7 +6,8 @@ The rule (include/sift_hip.h), restated: PI is one fixed permutation of 0..127,
     dot = chain(q, t), nq = chain(q, q), nt = chain(t, t),
     s = nq + nt (one float32 rounding), d = fmaf(-2.0f, dot, s), d = d < 0 ? 0 : d.
 d is the squared distance; neighbours ascend by (d, train index), a row at d =
-+inf is never one, missing entries are idx -1 / dist +inf.
++inf or at d = NaN (finite rows give inf - inf) is never one, missing entries are
+idx -1 / dist +inf, so the result holds no NaN.
 
 fma32() is a correctly rounded float32 fma in numpy, vectorised over pairs: the
 product of two float32 is exact in float64; the float64 sum with the addend is
@@ -43,7 +44,8 @@ def fma32(a, b, c):
     shape = a.shape
     p = a.astype(f64).ravel() * b.astype(f64).ravel()      # exact: 24 + 24 bits
     c64 = c.astype(f64).ravel()
-    s = p + c64                                            # rounded to 53 bits
+    with np.errstate(invalid="ignore"):
+        s = p + c64                                        # rounded to 53 bits (inf - inf: NaN)
     with np.errstate(over="ignore"):
         r = s.astype(f32)                                  # rounded again
     # a float32 midpoint has, as a float64, the low 29 fraction bits 1000...0 (normal
@@ -72,8 +74,8 @@ def chain(x, y, order=PI):
     return acc
 
 
-def distances(q, t, order=PI):
-    """[nq, nt] float32 d by the rule."""
+def distances(q, t, order=PI, clamp=True):
+    """[nq, nt] float32 d by the rule; clamp=False: the value before d < 0 ? 0 : d."""
     q, t = np.asarray(q, f32).reshape(-1, 128), np.asarray(t, f32).reshape(-1, 128)
     d = np.empty((len(q), len(t)), f32)
     if not len(q) or not len(t):
@@ -82,21 +84,24 @@ def distances(q, t, order=PI):
     step = max(1, 200000 // len(t))
     for a in range(0, len(q), step):
         dot = chain(q[a:a + step, None, :], t[None, :, :], order)
-        s = nq[a:a + step, None] + nt[None, :]             # float32 + float32: one rounding
+        with np.errstate(over="ignore"):
+            s = nq[a:a + step, None] + nt[None, :]         # float32 + float32: one rounding
         v = fma32(f32(-2), dot, s)
-        d[a:a + step] = np.where(v < 0, f32(0), v)
+        d[a:a + step] = np.where(v < 0, f32(0), v) if clamp else v
     return d
 
 
 def knn_from(d, k):
-    """(idx int32, dist float32) [nq, k] of a distance table: stable order on (d, index)."""
+    """(idx int32, dist float32) [nq, k] of a distance table: stable order on (d, index).
+    A NaN distance counts as +inf: strict '<' is false on it, as on +inf against an empty slot."""
+    d = np.where(np.isnan(d), f32(np.inf), d)
     idx = np.full((len(d), k), -1, np.int32)
     dist = np.full((len(d), k), np.inf, f32)
     order = np.argsort(d, axis=1, kind="stable")[:, :k]
     m = order.shape[1]
     if m and len(d):
         dd = np.take_along_axis(d, order, axis=1)
-        idx[:, :m] = np.where(np.isposinf(dd), -1, order)  # a row at +inf is never a neighbour
+        idx[:, :m] = np.where(np.isposinf(dd), -1, order)  # a row at +inf or NaN is never a neighbour
         dist[:, :m] = dd
     return idx, dist
 
@@ -299,3 +304,328 @@ def census(c, k_rows=None):
             first += int((d[:, 0] == d[:, 1]).sum())
             second += int(((d[:, 0] < d[:, 1]) & (d[:, 1] == d[:, 2])).sum())
     return first, second
+
+
+# ---- values: signs, cancellation, subnormals, overflow ----------------------------------
+# The four value cases share one shape.  Query segments of 33 and 65 rows: their last rows
+# are the last busy lane of a block with idle lanes behind it.  Train: 130 shared rows (three
+# splits: 64, 64 and a tail step of two rows), or ranges of 130 and 97 rows from row 3 (two
+# splits each: 128 and a tail of 2; 64 and a tail of 33).  The special rows of a case sit
+# either side of every seam of its ranges and on the last row of the tail step.
+V_Q, V_T, V_FIRST = [33, 65], [130, 97], 3
+
+
+def split_rows(q_cap, nseg, t_cap, seg_train, nt):
+    """Train rows per split of a range of nt rows: knn_l2_f32_seg_splits and the kernel's
+    `per` (match_l2_f32.hip), restated."""
+    gx = q_cap // Q_TILE + nseg
+    share = -(-t_cap // nseg) if seg_train else t_cap
+    splits = max(1, min(-(-1024 // gx), -(-share // T_STEP)))
+    return -(-(-(-nt // splits)) // T_STEP) * T_STEP
+
+
+def value_shape(seg_train, q_sizes=V_Q, t_sizes=V_T):
+    """(qoff, toff or None, train rows, [(first row, rows, rows per split)] per segment)."""
+    qoff = U.offsets(q_sizes)
+    nq, nseg = int(qoff[-1]), len(q_sizes)
+    if not seg_train:
+        return qoff, None, T_SHARED, [(0, T_SHARED, split_rows(nq, nseg, T_SHARED, False, T_SHARED))] * nseg
+    toff = U.offsets(t_sizes, V_FIRST)
+    n_t = int(toff[-1]) + 2
+    return qoff, toff, n_t, [(int(toff[b]), t_sizes[b], split_rows(nq, nseg, n_t, True, t_sizes[b]))
+                             for b in range(nseg)]
+
+
+def seams(nt, per):
+    """{s: kind}: local rows s with a seam between s - 1 and s -- a half-wave's four rows,
+    the 32-row tiles, the 64-row steps, the splits; the coarsest kind of each."""
+    out = {4: "half"} if nt > 4 else {}
+    out.update({s: "tile" for s in range(T_TILE, nt, T_TILE)})
+    out.update({s: "step" for s in range(T_STEP, nt, T_STEP)})
+    out.update({s: "split" for s in range(per, nt, per)})
+    return out
+
+
+def seam_rows(nt, per):
+    """The rows either side of every seam and the last row (of a tail step where nt % 64)."""
+    return sorted({r for s in seams(nt, per) for r in (s - 1, s)} | {nt - 1})
+
+
+def seg_tables(c):
+    """(b, first query row, queries, train rows) of every non-empty segment, on the clamped bounds."""
+    qo = U.clamped(c.qoff, c.q_cap)
+    to = None if c.toff is None else U.clamped(c.toff, c.t_cap)
+    for b in range(len(qo) - 1):
+        ts = c.t[:c.t_cap] if to is None else c.t[to[b]:max(to[b], to[b + 1])]
+        if qo[b + 1] > qo[b]:
+            yield b, int(qo[b]), c.q[qo[b]:qo[b + 1]], ts
+
+
+def subnormal(x):
+    """Non-zero and below 2^-126 in magnitude."""
+    x = np.abs(np.asarray(x, f64))
+    return (x > 0) & (x < 2.0 ** -126)
+
+
+# ---- signed rows --------------------------------------------------------------------------
+def signed_rows(rng, n):
+    """Non-dyadic rows uniform in [-0.4, 0.4)."""
+    return ((rng.random((n, 128), f32) - f32(0.5)) * f32(0.8)).astype(f32)
+
+
+@functools.lru_cache(maxsize=None)
+def signed_case(seg_train):
+    """Signed rows.  In every segment queries 2 and n - 2 are all zero.  The seam rows of a
+    train range are exact negations of a query (dot = -nq, d = 4 nq: the farthest row, and
+    the nearest, at 0, to a matcher blind to an operand's sign), alternately of the segment's
+    last query and of queries 1, 3, 5, ...; but row 31 of the first range (and of the shared
+    set) is all zero.  A zero row is at d = nq, about half the distance of any other, so it is
+    every query's nearest row: one such row leaves the second neighbour, and the whole of
+    the second range, to the signed rows."""
+    rng = np.random.default_rng(160 + seg_train)
+    qoff, toff, n_t, ranges = value_shape(seg_train)
+    nseg = len(qoff) - 1
+    q, t = signed_rows(rng, int(qoff[-1])), signed_rows(rng, n_t)
+    for b in range(nseg):
+        q[qoff[b] + 2] = 0
+        q[qoff[b + 1] - 2] = 0
+    negated = []                             # (segment, local query, local train row)
+    for b, (ts, nt, per) in enumerate(ranges if seg_train else ranges[:1]):
+        for i, r in enumerate(seam_rows(nt, per)):
+            if b == 0 and r == T_TILE - 1:
+                t[ts + r] = 0
+                continue
+            seg = b if seg_train else (i // 2) % nseg
+            j = int(qoff[seg + 1] - qoff[seg]) - 1 if i % 2 == 0 else i
+            t[ts + r] = -q[qoff[seg] + j]
+            negated.append((seg, j, r))
+    c = Case("f32-signed-" + ("segmented" if seg_train else "shared"), q, qoff, t, toff)
+    c.negated = negated
+    return c
+
+
+# ---- near-copies: the clamp -------------------------------------------------------------
+CANCEL_SEED = {False: 172, True: 171}        # chosen on the oracle alone: cancel_census() meets the test's counts
+CANCEL_PLANTED = {False: [20, 30], True: [28, 40]}   # planted queries per segment
+
+
+def cancel_pairs(nt, per, n):
+    """n disjoint (lo, hi, kind) pairs of local rows: four across every seam ((s - 1, s),
+    (s - 2, s + 1), ...), then consecutive free rows (kind "inside")."""
+    used, out = set(), []
+
+    def take(lo, hi, kind):
+        if 0 <= lo < hi < nt and not ({lo, hi} & used) and len(out) < n:
+            used.update((lo, hi))
+            out.append((lo, hi, kind))
+
+    for w in range(4):
+        for s, kind in seams(nt, per).items():
+            take(s - 1 - w, s + w, kind)
+    assert nt - 1 in used                    # the last row of the tail step holds a near-copy
+    free = [r for r in range(nt) if r not in used]
+    for lo, hi in zip(free[0::2], free[1::2]):
+        take(lo, hi, "inside")
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def cancel_case(seg_train):
+    """Near-duplicates.  A planted query has two near-copies among the train rows and no
+    exact copy: itself with one element moved one ulp up in one row, and another element one
+    ulp down in the other.  Their true distance, about 1e-16, is far below the rule's
+    absolute error (about 1e-4 here), so the sign of fmaf(-2, dot, s) is rounding noise and
+    the clamp decides the result.  A planted query is an ordinary row times 1/4 with the two
+    moved elements set to 1.5 .. 2: each carries close to half of the norm, so that its ulp
+    is about an ulp of the norm.  (On ordinary rows an element carries a fortieth of the
+    norm at most, its ulp changes no rounding of the chain, and fmaf(-2, dot, s) is exactly 0
+    on 98 % of such pairs: 0 to 4 non-zero values among 100 to 136 pairs, over 30 seeds.)
+    The pairs sit across the seams (cancel_pairs); the first planted query of a segment is
+    its last row.  c.planted: (query row, segment, lo, hi, kind)."""
+    rng = np.random.default_rng(CANCEL_SEED[seg_train])
+    qoff, toff, n_t, ranges = value_shape(seg_train)
+    nseg = len(qoff) - 1
+    q, t = rows(rng, int(qoff[-1])), rows(rng, n_t)
+    local = [[int(qoff[b + 1] - qoff[b]) - 1] + list(range(int(qoff[b + 1] - qoff[b]) - 1)) for b in range(nseg)]
+    counts = CANCEL_PLANTED[seg_train]
+    if seg_train:
+        plan = [(b, local[b][n], pair) for b, (ts, nt, per) in enumerate(ranges)
+                for n, pair in enumerate(cancel_pairs(nt, per, counts[b]))]
+    else:                                    # one train set: its pairs go to the segments in turn
+        slots = [(b, local[b][n]) for n in range(max(counts)) for b in range(nseg) if n < counts[b]]
+        plan = [s + (pair,) for s, pair in zip(slots, cancel_pairs(ranges[0][1], ranges[0][2], len(slots)))]
+    planted = []
+    for n, (b, j, (lo, hi, kind)) in enumerate(plan):
+        row, ts = int(qoff[b]) + j, ranges[b][0]
+        e_up, e_down = (int(e) for e in rng.choice(128, 2, replace=False))
+        q[row] *= f32(0.25)
+        q[row, [e_up, e_down]] = f32(1.5) + rng.random(2, f32) * f32(0.5)
+        up, down = (lo, hi) if n % 2 == 0 else (hi, lo)
+        t[ts + up] = q[row]
+        t[ts + up, e_up] = np.nextafter(q[row, e_up], f32(np.inf))
+        t[ts + down] = q[row]
+        t[ts + down, e_down] = np.nextafter(q[row, e_down], f32(-np.inf))
+        planted.append((row, b, lo, hi, kind))
+    c = Case("f32-cancel-" + ("segmented" if seg_train else "shared"), q, qoff, t, toff)
+    c.planted, c.ranges = planted, ranges
+    return c
+
+
+def cancel_census(c):
+    """Of the planted (query, near-copy) pairs: how many have fmaf(-2, dot, s) < 0 and > 0;
+    the kinds of the planted queries both of whose near-copies clamp to 0 (a tie, by index)."""
+    neg = pos = 0
+    tied = []
+    for row, b, lo, hi, kind in c.planted:
+        ts = c.ranges[b][0]
+        v = distances(c.q[row:row + 1], c.t[[ts + lo, ts + hi]], clamp=False)[0]
+        neg += int((v < 0).sum())
+        pos += int((v > 0).sum())
+        if (v <= 0).all():
+            tied.append(kind)
+    return neg, pos, tied
+
+
+# ---- subnormals -------------------------------------------------------------------------
+def subnormal_rows(rng, n):
+    """Rows of float32 subnormals (random fractions, either sign) with six normal elements of
+    about 2^-60 each."""
+    bits = rng.integers(1, 1 << 23, (n, 128)).astype(np.int32) | (rng.integers(0, 2, (n, 128)).astype(np.int32) << 31)
+    x = bits.view(f32).copy()
+    for i in range(n):
+        e = rng.choice(128, 6, replace=False)
+        x[i, e] = rows(rng, 1)[0, e] * f32(2.0 ** -58)
+    return x
+
+
+@functools.lru_cache(maxsize=None)
+def subnormal_case(seg_train):
+    """Rows of three kinds by (local row % 3), queries and train alike, so that every tile
+    and every seam mixes them: 0 -- ordinary rows times 2^-70 (normal elements; products,
+    dots and norms in the subnormal range or below it); 1 -- subnormal_rows(); 2 -- ordinary
+    rows.  The nearest rows of a kind-0 query are kind-0 rows at subnormal distances."""
+    rng = np.random.default_rng(180 + seg_train)
+    qoff, toff, n_t, ranges = value_shape(seg_train)
+    q, t = rows(rng, int(qoff[-1])), rows(rng, n_t)
+
+    def fill(x, first, n):
+        kind = np.arange(n) % 3
+        x[first:first + n][kind == 0] *= f32(2.0 ** -70)
+        x[first:first + n][kind == 1] = subnormal_rows(rng, int((kind == 1).sum()))
+
+    for b in range(len(qoff) - 1):
+        fill(q, int(qoff[b]), int(qoff[b + 1] - qoff[b]))
+    for ts, nt, _ in (ranges if seg_train else ranges[:1]):
+        fill(t, ts, nt)
+    return Case("f32-subnormal-" + ("segmented" if seg_train else "shared"), q, qoff, t, toff)
+
+
+def subnormal_census(c):
+    """(products q[e] t[e] in the subnormal range, subnormal distances in the table, NaN
+    distances in the table, subnormal distances in the k = 2 result)."""
+    prod = dsub = nan = 0
+    for _, _, qs, ts in seg_tables(c):
+        for a in range(0, len(qs), 16):
+            prod += int(subnormal(qs[a:a + 16, None, :].astype(f64) * ts[None, :, :].astype(f64)).sum())
+        d = distances(qs, ts)
+        dsub += int(subnormal(d).sum())
+        nan += int(np.isnan(d).sum())
+    return prod, dsub, nan, int(subnormal(c.dist).sum())
+
+
+# ---- overflow: +inf and NaN distances of finite rows -----------------------------------
+BIG_NORM = 2.4e38        # the norm of a big row: finite, and two of them sum past float32 (3.4e38)
+HUGE = f32(1e20)         # rows() times HUGE: elements up to 4e19, the norm +inf
+O_Q, O_T = [33, 65, 10], [130, 97, 9]
+
+
+def big(x):
+    """Rows scaled to a norm of BIG_NORM each: elements of about 1e18."""
+    return (x * np.sqrt(BIG_NORM / chain(x, x).astype(f64))[:, None]).astype(f32)
+
+
+def fused_pair(rng):
+    """Finite rows (y, t), near-copies of each other, with chain(y, y) and chain(t, t) below
+    2^127 and chain(y, t) >= 2^127: s = nq + nt is finite and -2 dot alone is -inf, but the
+    fused d = fmaf(-2, dot, s) is finite (negative: it clamps to 0).  Found by walking the
+    scale of one row up in ulps across 2^127 with 48 one-ulp jitters at each."""
+    x = rows(rng, 1)[0]
+    top = f32(2.0 ** 127)
+    scale = f32(np.sqrt(2.0 ** 127 / float(chain(x, x))) * (1 - 2.0 ** -20))
+    for _ in range(64):
+        base = (x * scale).astype(f32)[None, :].repeat(48, 0)
+        step = rng.integers(-1, 2, base.shape)
+        cand = np.where(step > 0, np.nextafter(base, f32(np.inf)), np.where(step < 0, np.nextafter(base, f32(0)), base))
+        cand = cand.astype(f32)
+        ok = np.nonzero(chain(cand, cand) < top)[0]
+        if len(ok) > 1:
+            dot = chain(cand[ok][:, None, :], cand[ok][None, :, :])
+            hit = [(i, j) for i, j in np.argwhere(dot >= top) if i != j]
+            if hit:
+                return cand[ok[hit[0][0]]], cand[ok[hit[0][1]]]
+        scale = np.nextafter(scale, f32(np.inf))
+    raise AssertionError("no fused pair found")
+
+
+@functools.lru_cache(maxsize=None)
+def overflow_case(seg_train):
+    """Finite elements only.  Train rows are ordinary ("o"), big(rows()) ("b": against a big
+    query s = +inf and d = +inf, against an ordinary one d is about 2e38), rows() * HUGE ("h":
+    nt = +inf; against a big query dot = +inf and d = inf - inf = NaN, against an ordinary one
+    d = +inf) or rows() * -HUGE ("n": dot = -inf against a big query, d = +inf).  Queries are
+    ordinary or big.  Against the ordinary train rows a big query has d = nq
+    for every one of them (2 dot and nt are below half an ulp of nq): a tie by index.
+    Range 0 (130 rows, shared too): h, n, b on rows 0..2, cycling over the seam rows and on
+    the last row, ordinary elsewhere; row 10 and query 5 are fused_pair().  Range 1 (97
+    rows): h, n, b cycling everywhere, h on the last row, one ordinary row (40): a big query
+    has one finite neighbour.  Range 2 (9 rows): h, n, b only, all ten queries big: none."""
+    rng = np.random.default_rng(190 + seg_train)
+    qoff, toff, n_t, ranges = value_shape(seg_train, O_Q if seg_train else V_Q, O_T)
+    nseg = len(qoff) - 1
+    q, t = rows(rng, int(qoff[-1])), rows(rng, n_t)
+    big_q = np.zeros(len(q), bool)
+    for b in range(nseg):
+        n = int(qoff[b + 1] - qoff[b])
+        big_q[qoff[b]:qoff[b + 1]] = [np.arange(n) % 2 == 1, np.arange(n) % 3 == 0, np.ones(n, bool)][b]
+        big_q[qoff[b + 1] - 1] = True        # the last query of every segment
+    q[big_q] = big(q[big_q])
+    kinds = np.full(n_t, "o")
+    for b, (ts, nt, per) in enumerate(ranges if seg_train else ranges[:1]):
+        if b == 0:
+            special = sorted(set(seam_rows(nt, per)) | {0, 1, 2})
+            kinds[[ts + r for r in special]] = [("h", "n", "b")[i % 3] for i in range(len(special))]
+        else:
+            kinds[ts:ts + nt] = [("h", "n", "b")[i % 3] for i in range(nt)]
+            if b == 1:
+                kinds[ts + 40] = "o"
+        kinds[ts + nt - 1] = "h"             # the last row of the tail step, the stand-in for its masked rows
+    t[kinds == "b"] = big(t[kinds == "b"])
+    t[kinds == "h"] *= HUGE
+    t[kinds == "n"] *= -HUGE
+    fused_q, fused_t = int(qoff[0]) + 5, ranges[0][0] + 10
+    q[fused_q], t[fused_t] = fused_pair(rng)
+    big_q[fused_q], kinds[fused_t] = True, "f"
+    assert np.isfinite(q).all() and np.isfinite(t).all()
+    c = Case("f32-overflow-" + ("segmented" if seg_train else "shared"), q, qoff, t, toff)
+    c.big_q, c.kinds, c.fused, c.ranges = big_q, kinds, (fused_q, fused_t), ranges
+    return c
+
+
+def overflow_census(c):
+    """Counts by the oracle: NaN and +inf distances in the tables; queries with two finite
+    neighbours of which the nearer has a NaN / +inf row before it in index order; queries
+    with exactly one finite neighbour; queries with none."""
+    out = dict(nan=0, inf=0, two_behind=0, one=0, none=0)
+    for _, q0, qs, ts in seg_tables(c):
+        d = distances(qs, ts)
+        out["nan"] += int(np.isnan(d).sum())
+        out["inf"] += int(np.isposinf(d).sum())
+        idx = c.idx[q0:q0 + len(qs)]
+        for i in range(len(qs)):
+            if idx[i, 1] >= 0:
+                out["two_behind"] += bool((~np.isfinite(d[i, :idx[i, 0]])).any())
+            elif idx[i, 0] >= 0:
+                out["one"] += 1
+            else:
+                out["none"] += 1
+    return out

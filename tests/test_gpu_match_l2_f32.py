@@ -3,7 +3,9 @@
 Every expected value is match_l2_f32_inputs' oracle -- the rule of sift_hip.h walked
 with a correctly rounded float32 fma -- compared bit for bit (indices and the float
 distances), into sentinel-filled outputs with extra rows.  On dyadic rows (u / 512)
-the result is also the byte squared-L2 matcher's, scaled by 2^-18."""
+the result is also the byte squared-L2 matcher's, scaled by 2^-18.  The value
+cases (signed rows, near-copies around the clamp, subnormals, +inf and NaN
+distances of finite rows) pin the lines of the rule that depend on values."""
 import numpy as np
 import pytest
 
@@ -253,3 +255,102 @@ def test_gpu_l2_f32_rule_against_float64_on_real_descriptors(ctx):
         idx, dist = ctx.knnMatchL2SqrF32(q, t, 2)
         exempt = T.check_against_float64(name, q, t, idx, dist)
         assert exempt <= 0.01 * len(q), (name, exempt, len(q))
+
+
+# ---- values: signs, cancellation, subnormals, overflow -------------------------------------
+VALUE_CASES = {"signed": F.signed_case, "cancel": F.cancel_case, "subnormal": F.subnormal_case,
+               "overflow": F.overflow_case}
+
+
+@pytest.mark.parametrize("k", [2, 1])
+@pytest.mark.parametrize("seg_train", [False, True], ids=["shared", "segmented"])
+@pytest.mark.parametrize("name", list(VALUE_CASES))
+def test_gpu_l2_f32_value_cases(ctx, name, seg_train, k):
+    """Signed rows with negated and zero rows; near-copies whose fmaf(-2, dot, s) is rounding
+    noise either side of 0; subnormal elements, products, norms and distances; finite rows
+    whose distances are +inf and NaN.  The special rows sit either side of the half-wave,
+    tile, step and split seams, on the last row of a tail step and on the last query of
+    segments of 33 and 65.  No NaN reaches the result; idx and dist equal the oracle's bit
+    for bit; rows outside the live range are untouched."""
+    c = VALUE_CASES[name](seg_train)
+    ridx, rdist = c.ref(k)
+    assert not np.isnan(rdist).any()
+    idx, dist = _f32_device(ctx, c, k)
+    live = slice(int(c.qoff[0]), int(c.qoff[-1]))
+    bad = np.nonzero(((idx[live] != ridx[live]) | (dist[live].view(np.int32) != rdist[live].view(np.int32))).any(axis=1))[0]
+    for r in bad[:8]:
+        print(f"{c.name} k={k} row {r}: idx {idx[r].tolist()} dist {dist[r].tolist()}, "
+              f"oracle {ridx[r].tolist()} {rdist[r].tolist()}")
+    print(f"{c.name} k={k}: {len(bad)} of {live.stop - live.start} rows differ from the oracle")
+    assert not np.isnan(dist[live]).any(), c.name
+    B._check_live(idx, dist, ridx, rdist, c.qoff, c.q_cap, f"{c.name} k={k}")
+
+
+@pytest.mark.parametrize("name", ["cancel", "overflow"])
+def test_gpu_l2_f32_value_cases_host_forms_and_roots(ctx, siftgpu, name):
+    """The host segmented form and the one-segment form equal the device form, and
+    l2_match(squared=False) returns the float32 square roots of the oracle's distances: 0
+    stays 0, an entry at -1 / +inf is no match and its root in the table stays +inf."""
+    for seg_train in (False, True):
+        c = VALUE_CASES[name](seg_train)
+        for k in (2, 1):
+            di, dd = _f32_device(ctx, c, k, extra=0)
+            hi, hd = ctx.knnMatchL2SqrF32Segmented(c.q, c.qoff, c.t, c.toff, k)
+            assert_bits_equal(hi, di, f"{c.name} host idx equals device k={k}")
+            assert_bits_equal(hd, dd, f"{c.name} host dist equals device k={k}")
+            assert_bits_equal(hi, c.ref(k)[0], f"{c.name} host idx k={k}")
+            assert_bits_equal(hd, c.ref(k)[1], f"{c.name} host dist k={k}")
+        zeros = missing = 0
+        for b, q0, qs, ts in F.seg_tables(c):
+            ridx, rdist = c.idx[q0:q0 + len(qs)], c.dist[q0:q0 + len(qs)]
+            oi, od = ctx.knnMatchL2SqrF32(qs, ts, 2)
+            assert_bits_equal(oi, ridx, f"{c.name}[{b}] one-segment idx")
+            assert_bits_equal(od, rdist, f"{c.name}[{b}] one-segment dist")
+            root = np.sqrt(rdist)
+            assert root.dtype == np.float32 and (root[rdist == 0].view(np.int32) == 0).all()
+            assert np.isposinf(root[ridx < 0]).all() and np.isfinite(root[ridx >= 0]).all()
+            lists = siftgpu.l2_match(qs, ts, 2, squared=False, ctx=ctx)
+            assert [[m.trainIdx for m in row] for row in lists] == [[int(i) for i in r if i >= 0] for r in ridx]
+            assert [[m.distance for m in row] for row in lists] == \
+                [[float(d) for i, d in zip(ri, rd) if i >= 0] for ri, rd in zip(ridx, root)]
+            assert [[m.queryIdx for m in row] for row in lists] == [[n] * int((r >= 0).sum()) for n, r in enumerate(ridx)]
+            zeros, missing = zeros + int((rdist == 0).sum()), missing + int((ridx < 0).sum())
+        assert zeros >= 1 and (name == "cancel" or not seg_train or missing >= 8)
+
+
+def test_gpu_l2_f32_overflow_ratio_stage_in_stream_order(ctx, siftgpu):
+    """The matcher on overflow_case and the ratio stage at 0.86^2 on its tables, enqueued one
+    behind the other with one sync: no query whose second neighbour is -1 is kept (its d1 <=
+    ratio * +inf holds as numbers), and the records are those of the oracle's tables."""
+    import torch
+    c = F.overflow_case(True)
+    n = c.q_cap
+    dq, dqo, dt, dto = B._dev(c.q), B._dev(c.qoff), B._dev(c.t), B._dev(c.toff)
+    di = torch.full((n, 2), U.SENT_I, dtype=torch.int32, device="cuda")
+    dd = torch.full((n, 2), U.SENT_D, dtype=torch.float32, device="cuda")
+    dm = torch.full((n + 8, 4), -77, dtype=torch.int32, device="cuda")
+    ds = torch.full((n + 8, 2), -5.0, dtype=torch.float32, device="cuda")
+    dst = torch.full((n + 8, 2), -5.0, dtype=torch.float32, device="cuda")
+    dmo = torch.full((len(c.qoff),), -77, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    nseg = len(c.qoff) - 1
+    ctx.knn_match_l2sqr_f32_segmented_device(dq.data_ptr(), dqo.data_ptr(), nseg, n, dt.data_ptr(), dto.data_ptr(),
+                                             c.t_cap, 2, di.data_ptr(), dd.data_ptr())
+    ctx.ratio_matches_device(di.data_ptr(), dd.data_ptr(), dqo.data_ptr(), nseg, n, RATIO2, None, None, None,
+                             dm.data_ptr(), ds.data_ptr(), dst.data_ptr(), n, dmo.data_ptr())
+    ctx.sync()
+    idx, dist = di.cpu().numpy(), dd.cpu().numpy()
+    assert not np.isnan(dist).any()
+    assert_bits_equal(idx, c.idx, "idx")
+    assert_bits_equal(dist, c.dist, "dist")
+    rec, rmoff, _, _ = B._ref_ratio(c.idx, c.dist, c.qoff, n, RATIO2)
+    m = dm.cpu().numpy().view(siftgpu.MATCH_DTYPE).reshape(-1)
+    kept = len(rec)
+    one = (c.idx[:, 0] >= 0) & (c.idx[:, 1] < 0)
+    assert kept >= 1 and one.sum() >= 8
+    assert_bits_equal(dmo.cpu().numpy(), rmoff, "m_offsets")
+    assert_bits_equal(m[:kept], B._rec_array(siftgpu, rec), "records")
+    assert (m[kept:].view(np.int32) == -77).all()
+    for r in m[:kept]:
+        row = int(c.qoff[r["segment"]]) + int(r["query"])
+        assert c.idx[row, 1] >= 0 and not one[row]

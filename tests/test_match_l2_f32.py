@@ -4,7 +4,9 @@ The exports, the null-context checks, the Python names, the layout program, and
 the oracle of match_l2_f32_inputs on its own: its float32 fma against libm's
 fmaf, the dyadic identity against the integer reference, a census of rows whose
 bits depend on the summation order, a census of the planted ties, and the
-rule's error bound on real descriptors against float64."""
+rule's error bound on real descriptors against float64; the NaN rule of
+knn_from, and the censuses of the value cases (signed rows, near-copies around
+the clamp, subnormals, overflow) with the mutations of the rule they tell apart."""
 import ctypes
 import ctypes.util
 import inspect
@@ -208,3 +210,200 @@ def test_oracle_rule_against_float64_on_real_descriptors():
         idx, dist = F.knn_ref(q, t, 2)
         exempt = check_against_float64(name, q, t, idx, dist)
         assert exempt <= 0.01 * len(q), (name, exempt, len(q))
+
+
+# ---- values: the NaN rule, signs, cancellation, subnormals, overflow ---------------------
+def test_knn_from_treats_nan_as_inf():
+    """A row at a NaN distance is never a neighbour, exactly like one at +inf; the missing
+    entries are -1 / +inf and no NaN reaches the result."""
+    nan, inf = np.nan, np.inf
+    d = np.array([[nan, 1.0, inf, 0.5], [nan, inf, nan, inf], [nan, 2.0, nan, nan], [0.0, nan, 0.0, -0.0]], f32)
+    idx, dist = F.knn_from(d, 2)
+    assert idx.tolist() == [[3, 1], [-1, -1], [1, -1], [0, 2]]
+    assert_bits_equal(dist, np.array([[0.5, 1.0], [inf, inf], [2.0, inf], [0.0, 0.0]], f32), "dist")
+    assert F.knn_from(d, 1)[0].tolist() == [[3], [-1], [1], [0]]
+
+
+class _Dyadic:
+    """The float form of a byte case, as the GPU test feeds it."""
+
+    def __init__(self, u):
+        self.name, self.qoff, self.toff, self.q_cap, self.t_cap = u.name, u.qoff, u.toff, u.q_cap, u.t_cap
+        self.q, self.t = F.dyadic(u.q), F.dyadic(u.t)
+
+
+def test_no_case_from_before_the_nan_rule_has_a_nan_distance():
+    """knn_from's NaN rule changes no expected value that existed before it: no distance of
+    any earlier case is NaN (nor infinite, nor negative), scored pair by scored pair."""
+    cases = [F.edges_case(False), F.edges_case(True), F.splits_case(), F.many_segments_case(), F.weights_case()]
+    cases += F.clamp_cases() + [_Dyadic(u) for u in F.dyadic_sources()]
+    pairs = 0
+    for c in cases:
+        dyadic = isinstance(c, _Dyadic)
+        for _, _, qs, ts in F.seg_tables(c):
+            if dyadic and len(qs) * len(ts) > 20000:
+                # the large byte cases: elements in [0, 0.5), so every norm and |dot| is at most
+                # 32 and fmaf(-2, dot, s) is finite; the first and last queries stand for the table
+                assert (qs >= 0).all() and (qs < 0.5).all() and (ts >= 0).all() and (ts < 0.5).all(), c.name
+                qs = np.concatenate([qs[:16], qs[-16:]])
+            d = F.distances(qs, ts)
+            assert np.isfinite(d).all() and (d >= 0).all(), c.name
+            pairs += d.size
+    print(f"{len(cases)} cases, {pairs} scored pairs, none NaN")
+    assert pairs > 100000
+
+
+def _float64_by_segment(c):
+    exempt = 0
+    for b, q0, qs, ts in F.seg_tables(c):
+        exempt += check_against_float64(f"{c.name}[{b}]", qs, ts, c.idx[q0:q0 + len(qs)], c.dist[q0:q0 + len(qs)])
+    return exempt
+
+
+@pytest.mark.parametrize("seg_train", [False, True], ids=["shared", "segmented"])
+def test_signed_case_census(seg_train):
+    """At least a quarter of all dots are negative; a zero query against a zero train row
+    gives d = +0.0 in bits; a negated query is at d = 4 nq up to the rule's bound, the
+    farthest row of its query; and the rule's float64 bound holds on signed rows."""
+    c = F.signed_case(seg_train)
+    assert (c.q < 0).mean() > 0.4 and (c.t < 0).mean() > 0.4
+    neg = total = zero_pairs = 0
+    for b, q0, qs, ts in F.seg_tables(c):
+        dot = F.chain(qs[:, None, :], ts[None, :, :])
+        neg, total = neg + int((dot < 0).sum()), total + dot.size
+        d = F.distances(qs, ts)
+        zq, zt = ~qs.any(axis=1), ~ts.any(axis=1)
+        assert zq.sum() == 2 and zt.sum() == (b == 0 or not seg_train)
+        zero_pairs += int((d[np.ix_(zq, zt)].view(np.int32) == 0).sum())
+        assert (d[np.ix_(zq, zt)].view(np.int32) == 0).all()
+        for seg, j, r in c.negated:
+            if seg == b:
+                nq = float(F.chain(qs[j], qs[j]))
+                assert dot[j, r] == -F.chain(qs[j], qs[j]) and abs(float(d[j, r]) - 4 * nq) <= 4 * GAMMA130 * nq
+                assert d[j, r] == d[j].max()
+    print(f"{c.name}: {neg} of {total} dots negative, {zero_pairs} zero pairs at +0.0, {len(c.negated)} negated rows")
+    assert 4 * neg >= total and zero_pairs >= 1 and len(c.negated) >= 6
+    assert np.isfinite(c.dist).all()
+    _float64_by_segment(c)
+
+
+@pytest.mark.parametrize("seg_train", [False, True], ids=["shared", "segmented"])
+def test_cancel_case_census(seg_train):
+    """Of the planted (query, near-copy) pairs at least 16 have fmaf(-2, dot, s) < 0 and at
+    least 16 have it > 0; at least 4 planted queries have both near-copies clamped to 0 (a
+    tie by index), one of them across a tile seam that is no split seam and one across a
+    split seam.  Every planted distance is within the rule's bound B of 0, and the float64
+    nearest two of a planted query are its two near-copies, as are the oracle's."""
+    c = F.cancel_case(seg_train)
+    neg, pos, tied = F.cancel_census(c)
+    print(f"{c.name}: {2 * len(c.planted)} planted pairs, {neg} below 0, {pos} above, {len(tied)} tied queries: "
+          + ", ".join(f"{tied.count(k)} {k}" for k in sorted(set(tied))))
+    assert len(c.planted) >= 32
+    assert neg >= 16 and pos >= 16 and len(tied) >= 4 and "tile" in tied and "split" in tied
+    kinds = {kind for *_, kind in c.planted}
+    assert {"half", "tile", "split"} <= kinds and (seg_train or "step" not in kinds)   # shared: every step seam a split seam
+    segs = {b: (q0, qs, ts) for b, q0, qs, ts in F.seg_tables(c)}
+    for b, (q0, qs, ts) in segs.items():
+        assert any(row == q0 + len(qs) - 1 for row, *_ in c.planted)           # the segment's last query
+        assert any(hi == len(ts) - 1 for _, pb, _, hi, _ in c.planted if pb == b or not seg_train)   # the tail's last row
+    for row, b, lo, hi, kind in c.planted:
+        q0, qs, ts = segs[b]
+        q64, t64 = qs[row - q0].astype(np.float64), ts.astype(np.float64)
+        d64 = ((q64[None, :] - t64) ** 2).sum(-1)
+        assert (d64 > 0).all()                                                    # no exact copy
+        assert sorted(np.argsort(d64, kind="stable")[:2].tolist()) == [lo, hi] and d64[[lo, hi]].max() < 1e-13
+        bound = 2 * GAMMA130 * ((q64 ** 2).sum() + (t64[[lo, hi]] ** 2).sum(-1))
+        assert sorted(c.idx[row].tolist()) == [lo, hi]
+        assert (c.dist[row].astype(np.float64) <= bound.min()).all()
+        if (c.dist[row] == 0).all():
+            assert c.idx[row].tolist() == [lo, hi]                                # the tie, by index
+    exempt = _float64_by_segment(c)
+    assert exempt <= len(c.planted)          # only the planted rows have no gap to rank by
+
+
+@pytest.mark.parametrize("seg_train", [False, True], ids=["shared", "segmented"])
+def test_subnormal_case_census(seg_train):
+    """At least 1000 products q[e] t[e] lie in the subnormal range, at least 100 distances
+    are subnormal and not zero, none is NaN; the expected result itself holds subnormal
+    distances (the nearest rows of the 2^-70 queries), and subnormal elements are present."""
+    c = F.subnormal_case(seg_train)
+    prod, dsub, nan, in_result = F.subnormal_census(c)
+    print(f"{c.name}: {prod} subnormal products, {dsub} subnormal distances, {in_result} of them in the result")
+    assert prod >= 1000 and dsub >= 100 and nan == 0 and in_result >= 20
+    assert F.subnormal(c.q).sum() >= 1000 and F.subnormal(c.t).sum() >= 1000
+    assert np.isfinite(c.dist).all() and (c.idx >= 0).all()
+    for _, _, qs, ts in F.seg_tables(c):     # the norms of the 2^-70 rows are subnormal, and not zero
+        assert F.subnormal(F.chain(qs[0::3], qs[0::3])).all() and F.subnormal(F.chain(ts[0::3], ts[0::3])).all()
+
+
+@pytest.mark.parametrize("seg_train", [False, True], ids=["shared", "segmented"])
+def test_overflow_case_census(seg_train):
+    """Finite rows give at least 8 NaN and 8 +inf distances; queries with two finite
+    neighbours behind NaN / +inf rows, with exactly one ([i, -1] / [d, +inf]) and with none
+    ([-1, -1]) occur (the last two in the segmented case); -2 dot alone overflows on the
+    fused pair, whose d clamps to 0; the expected result holds no NaN."""
+    c = F.overflow_case(seg_train)
+    assert np.isfinite(c.q).all() and np.isfinite(c.t).all()
+    n = F.overflow_census(c)
+    print(f"{c.name}: {n}")
+    assert n["nan"] >= 8 and n["inf"] >= 8 and n["two_behind"] >= 8
+    if seg_train:
+        assert n["one"] >= 8 and n["none"] >= 8
+    assert not np.isnan(c.dist).any()
+    assert ((c.idx < 0) == np.isposinf(c.dist)).all()
+    one = (c.idx[:, 0] >= 0) & (c.idx[:, 1] < 0)
+    assert np.isfinite(c.dist[one, 0]).all()
+    # the tail step's last row and both sides of a split seam give NaN or +inf
+    for b, q0, qs, ts in F.seg_tables(c):
+        nt, per = c.ranges[b][1], c.ranges[b][2]
+        d = F.distances(qs, ts)
+        big = c.big_q[q0:q0 + len(qs)]
+        assert np.isnan(d[big, nt - 1]).all() and np.isposinf(d[~big, nt - 1]).all()
+        for s, kind in F.seams(nt, per).items():
+            if kind == "split":
+                assert not np.isfinite(d[big][:, [s - 1, s]]).any()
+    fq, ft = c.fused
+    y, t = c.q[fq], c.t[ft]
+    dot, nq, nt = F.chain(y, t), F.chain(y, y), F.chain(t, t)
+    with np.errstate(over="ignore"):
+        assert np.isneginf(f32(-2) * dot) and np.isfinite(nq + nt)
+    v = F.distances(y, t, clamp=False)[0, 0]
+    assert np.isfinite(v) and v <= 0 and c.dist[fq, 0] == 0 and c.idx[fq, 0] == ft - c.ranges[0][0]
+    # a big query is at d = nq from every ordinary row: its neighbours are the first two by index
+    ordinary = np.nonzero(c.kinds[c.ranges[0][0]:c.ranges[0][0] + c.ranges[0][1]] == "o")[0][:2]
+    row = int(c.qoff[1]) - 1                 # the last query of segment 0, a big one
+    assert c.idx[row].tolist() == ordinary.tolist() and c.dist[row, 0] == c.dist[row, 1] == F.chain(c.q[row], c.q[row])
+
+
+def _mutant(c, how):
+    """The k = 2 result of a rule that differs from sift_hip.h's in one line."""
+    idx = np.full((c.q_cap, 2), -1, np.int32)
+    dist = np.full((c.q_cap, 2), np.inf, f32)
+    for _, q0, qs, ts in F.seg_tables(c):
+        v = F.distances(np.abs(qs) if how == "fabs" else qs, ts, clamp=False)
+        with np.errstate(invalid="ignore"):
+            d = {"no-clamp": v, "fmax": np.fmax(v, f32(0)), "fabs": np.where(v < 0, f32(0), v),
+                 "nan-inserted": np.where(v < 0, f32(0), v)}[how]
+        if how == "nan-inserted":            # a NaN that compares below everything, as a total order would have it
+            d = np.where(np.isnan(d), f32(-1), d)
+        idx[q0:q0 + len(qs)], dist[q0:q0 + len(qs)] = F.knn_from(d, 2)
+    return idx, dist
+
+
+@pytest.mark.parametrize("how, case", [("no-clamp", F.cancel_case), ("fmax", F.overflow_case),
+                                       ("nan-inserted", F.overflow_case), ("fabs", F.signed_case)])
+def test_value_cases_tell_the_rule_from_its_mutations(how, case):
+    """Dropping the clamp, writing it as fmaxf (NaN becomes 0), letting a NaN distance into
+    the list, or taking the magnitude of an operand: each changes the expected result of
+    the case made for it, shared and segmented, and none changes the result of a case that
+    existed before (whose GPU tests therefore cannot tell)."""
+    for seg_train in (False, True):
+        c = case(seg_train)
+        idx, dist = _mutant(c, how)
+        rows = int(((idx != c.idx) | (dist.view(np.int32) != c.dist.view(np.int32))).any(axis=1).sum())
+        print(f"{how}: {rows} rows of {c.name} differ")
+        assert rows >= 8
+    for old in (F.edges_case(True), F.splits_case(), F.weights_case()):
+        idx, dist = _mutant(old, how)
+        assert_bits_equal(idx, old.idx, old.name + " idx under " + how)
+        assert_bits_equal(dist, old.dist, old.name + " dist under " + how)

@@ -1024,6 +1024,79 @@ int sift_estimate_affine_segmented(sift_ctx* ctx, const float* src_xy, const flo
                                    int n_segments, int m_cap, int model, double ransac_thresh, int max_iters,
                                    double confidence, double* H, int* found, unsigned char* inlier_mask /* may be NULL */);
 
+/* ---- fundamental matrix ----------------------------------------------------- */
+/* `findFundamentalMat(points1, points2, FM_RANSAC)`: the third motion model, for
+ * stereo pairs, structure from motion and video with parallax, where no planar
+ * model fits.  n point pairs as interleaved (x, y) floats; OpenCV's defaults are
+ * ransac_thresh 3, max_iters 1000, confidence 0.99.  F is a row-major 3x3 with
+ * [dst; 1]^T F [src; 1] = 0 (OpenCV's convention), of rank 2; inlier_mask (n
+ * bytes, may be NULL) gets the RANSAC inliers.  Host code, no context.
+ * SIFT_E_INVALID (F and the mask zeroed) when no model is found, n < 8,
+ * max_iters < 1 or confidence outside (0, 1).
+ * The rule (csrc/fundamental_math.hpp) is sift_find_homography's loop with 8 in
+ * place of 4: n == 8 is a direct fit with no subset check and a mask of ones
+ * (none when the solve fails); otherwise subsets of 8 distinct rows from
+ * RNG(~0), accepted when the last drawn point is collinear with no two earlier
+ * ones in src and in dst (at most 10000 draws per hypothesis), a hypothesis wins
+ * iff it has more than max(best, 7) inliers, and max_iters shrinks after every
+ * win.
+ * The solve, for a hypothesis and for the final model, is the normalised
+ * 8-point algorithm in double, every sum in pair order: per image the centroid
+ * (the float coordinates summed, divided by the count) and the scale sqrt(2) /
+ * (mean of sqrt(dx^2 + dy^2)) -- a mean distance below DBL_EPSILON or a
+ * non-finite one fails the solve --; the nine-term row [X x, X y, X, Y x, Y y,
+ * Y, x, y, 1] over normalised coordinates (x, y src; X, Y dst); the 45 sums of
+ * A^T A's upper triangle, mirrored; f = the eigenvector of its smallest
+ * eigenvalue (the homography's cyclic Jacobi); rank 2 by F0 <- F0 - (F0 v) v^T
+ * with v the eigenvector of the smallest eigenvalue of F0^T F0 (the same Jacobi
+ * at 3x3: (F0 v) v^T is the sigma_3 u_3 v_3^T term of the SVD); F = T_dst^T F0
+ * T_src, divided by F[8] when |F[8]| > FLT_EPSILON (OpenCV's rule; otherwise
+ * left as it is); a non-finite entry fails the solve.
+ * A pair is an inlier iff, with the nine coefficients cast to float and unfused
+ * float arithmetic left to right, max(d_dst^2 s_dst, d_src^2 s_src) <=
+ * (float)(thr * thr): the squared distances of each point to the other's
+ * epipolar line, s = 1 / (a^2 + b^2) of that line.  A NaN error is never an
+ * inlier.  The final model is the same solve over the best hypothesis's inliers
+ * (a failed or non-finite refit leaves the RANSAC model); the mask is the best
+ * hypothesis's, taken before the refit.  There is no Levenberg-Marquardt or
+ * Sampson refinement and no 7-point solver (n == 7 gives none).
+ * The library's own rule, not bit-compatible with OpenCV: parity is pinned only
+ * against tests/fundamental_oracle.py, which restates the same steps.
+ * thr = -3 behaves as 3, thr = 0 admits only an exact zero error, and a thr
+ * whose square overflows float to +inf admits every pair with a finite or
+ * infinite (not NaN) error, so the first hypothesis ends the loop.
+ * Non-finite coordinates: the call terminates (every loop is bounded by a
+ * count), a hypothesis with a non-finite coefficient is no model, a row with a
+ * NaN coordinate is never an inlier, one with an infinite coordinate only under
+ * the +inf limit above; what the pair set as a whole gives (found, F) is
+ * otherwise unspecified, but F is always finite when found.  In the segmented
+ * forms below the other segments are unaffected. */
+int sift_find_fundamental(const float* src_xy, const float* dst_xy, int n, double ransac_thresh, int max_iters,
+                          double confidence, double* F, unsigned char* inlier_mask);
+
+/* The same for every segment of a batch, on the device in stream order, with
+ * the contract of sift_estimate_affine_segmented_device: segment b's pairs are
+ * rows [clamp(m_offsets[b]), clamp(m_offsets[b+1])) of d_src_xy / d_dst_xy,
+ * clamped to m_cap, and each segment gets exactly what sift_find_fundamental
+ * gives for its pairs, bit for bit.  d_F is [n_segments][9] row-major.
+ * d_found[b] is 1 for a model, 0 for none, and then F[b] is nine zeros and the
+ * segment's mask bytes are 0.  max_iters < 1 or confidence outside (0, 1) gives
+ * every segment found = 0.  d_inlier_mask is [m_cap] bytes by pair row and may
+ * be NULL; bytes outside [clamp(m_offsets[0]), clamp(m_offsets[n_segments])) and
+ * rows of d_F / d_found past n_segments are never written.
+ * Enqueued on the context stream, no synchronisation, no scratch, no host value
+ * read.  A NULL context: SIFT_E_INVALID.  n_segments == 0 or m_cap == 0:
+ * SIFT_OK, nothing enqueued.  A NULL required buffer: SIFT_E_INVALID
+ * (sift_last_error names it). */
+int sift_find_fundamental_segmented_device(sift_ctx* ctx, const float* d_src_xy, const float* d_dst_xy,
+                                           const int* d_m_offsets, int n_segments, int m_cap, double ransac_thresh,
+                                           int max_iters, double confidence, double* d_F, int* d_found,
+                                           unsigned char* d_inlier_mask /* may be NULL */);
+/* Host buffers (synchronous); src_xy / dst_xy have m_cap rows: */
+int sift_find_fundamental_segmented(sift_ctx* ctx, const float* src_xy, const float* dst_xy, const int* m_offsets,
+                                    int n_segments, int m_cap, double ransac_thresh, int max_iters, double confidence,
+                                    double* F, int* found, unsigned char* inlier_mask /* may be NULL */);
+
 /* ---- self-test ------------------------------------------------------------ */
 /* Evaluates one device arithmetic helper element-wise on host arrays (n
  * values), for bit-exact checks of the GPU math against the CPU oracle:

@@ -4,7 +4,8 @@
 // point pairs, the cross-check stage with its one-call form, the BGR8 front
 // end and the doubled image, each in a device and a host form, the one-pair
 // homography wrappers, the segmented homography and corner transform, the
-// affine / similarity estimate (one pair set and segmented), and the
+// affine / similarity estimate and the fundamental matrix (each one pair set
+// and segmented; fundamental.hip, fundamental_batch.hip), and the
 // perspective warp of a batch.  Host code only; the kernels live in match.hip,
 // match_u8.hip, match_l2_u8.hip, match_l2_f32.hip, match_window.hip, cross_check.hip,
 // frontend.hip, upsample.hip, homography_batch.hip, affine_batch.hip and warp.hip (the one-pair
@@ -440,6 +441,19 @@ int affine_device(sift_ctx* c, const float* src_xy, const float* dst_xy, const i
     StageScope sc(c, ST_AFFINE_SEG);  // the work depends on offsets and points only the device knows
     launch_affine_seg(c->stream, src_xy, dst_xy, moff, n_segments, m_cap, model, thr, max_iters, confidence, H, found,
                       mask_out);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
+// ---- a whole batch: findFundamentalMat(FM_RANSAC) per segment of the same pairs ----
+int fundamental_device(sift_ctx* c, const float* src_xy, const float* dst_xy, const int* moff, int n_segments,
+                       int m_cap, double thr, int max_iters, double confidence, double* F, int* found,
+                       unsigned char* mask_out) {
+  {
+    StageScope sc(c, ST_FUND_SEG);  // the work depends on offsets and points only the device knows
+    launch_fundamental_seg(c->stream, src_xy, dst_xy, moff, n_segments, m_cap, thr, max_iters, confidence, F, found,
+                           mask_out);
   }
   HIP_TRY(c, hipGetLastError());
   return SIFT_OK;
@@ -947,6 +961,54 @@ int sift_estimate_affine_segmented(sift_ctx* c, const float* src_xy, const float
                           confidence, S.H, S.found, inlier_mask ? S.mask : nullptr)))
     return rc;
   HIP_TRY(c, hipMemcpyAsync(H, S.H, (size_t)n_segments * 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(found, S.found, (size_t)n_segments * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  // only the segments' mask bytes come back: the others are left untouched, as in the device form
+  const int lo = clamp_off(m_offsets[0], m_cap), hi = clamp_off(m_offsets[n_segments], m_cap);
+  if (inlier_mask && hi > lo)
+    HIP_TRY(c, hipMemcpyAsync(inlier_mask + lo, S.mask + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SIFT_OK;
+}
+
+// ---- findFundamentalMat(FM_RANSAC): one pair set on the host, a batch on the device ----
+int sift_find_fundamental(const float* src_xy, const float* dst_xy, int n, double ransac_thresh, int max_iters,
+                          double confidence, double* F, unsigned char* inlier_mask) {
+  if (!src_xy || !dst_xy || !F || n < 0) return SIFT_E_INVALID;
+  if (!find_fundamental_ransac(src_xy, dst_xy, n, ransac_thresh, max_iters, confidence, F, inlier_mask)) {
+    for (int i = 0; i < 9; ++i) F[i] = 0;  // OpenCV returns an empty Mat
+    if (inlier_mask) memset(inlier_mask, 0, (size_t)n);
+    return SIFT_E_INVALID;
+  }
+  return SIFT_OK;
+}
+
+int sift_find_fundamental_segmented_device(sift_ctx* c, const float* d_src_xy, const float* d_dst_xy,
+                                           const int* d_m_offsets, int n_segments, int m_cap, double ransac_thresh,
+                                           int max_iters, double confidence, double* d_F, int* d_found,
+                                           unsigned char* d_inlier_mask) {
+  int rc = check_homog(c, d_src_xy, d_dst_xy, d_m_offsets, n_segments, m_cap, d_F, d_found);
+  if (rc || n_segments == 0 || m_cap == 0) return rc;
+  (void)hipSetDevice(c->device);
+  return fundamental_device(c, d_src_xy, d_dst_xy, d_m_offsets, n_segments, m_cap, ransac_thresh, max_iters,
+                            confidence, d_F, d_found, d_inlier_mask);
+}
+
+int sift_find_fundamental_segmented(sift_ctx* c, const float* src_xy, const float* dst_xy, const int* m_offsets,
+                                    int n_segments, int m_cap, double ransac_thresh, int max_iters, double confidence,
+                                    double* F, int* found, unsigned char* inlier_mask) {
+  int rc = check_homog(c, src_xy, dst_xy, m_offsets, n_segments, m_cap, F, found);
+  if (rc || n_segments == 0 || m_cap == 0) return rc;
+  (void)hipSetDevice(c->device);
+  AffineHost S;  // the same staging as the affine estimate's (scratch.hpp)
+  if ((rc = carve(c, &S, [&](Carver& a) { return affine_host_layout(a, n_segments, m_cap); }))) return rc;
+  const size_t xyb = (size_t)m_cap * 2 * sizeof(float), ob = (size_t)(n_segments + 1) * sizeof(int);
+  HIP_TRY(c, hipMemcpyAsync(S.src_xy, src_xy, xyb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.dst_xy, dst_xy, xyb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.m_off, m_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  if ((rc = fundamental_device(c, S.src_xy, S.dst_xy, S.m_off, n_segments, m_cap, ransac_thresh, max_iters,
+                               confidence, S.H, S.found, inlier_mask ? S.mask : nullptr)))
+    return rc;
+  HIP_TRY(c, hipMemcpyAsync(F, S.H, (size_t)n_segments * 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(found, S.found, (size_t)n_segments * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   // only the segments' mask bytes come back: the others are left untouched, as in the device form
   const int lo = clamp_off(m_offsets[0], m_cap), hi = clamp_off(m_offsets[n_segments], m_cap);

@@ -296,6 +296,13 @@ int estimate_affine_ransac(const float* src_xy, const float* dst_xy, int n, int 
 void launch_affine_seg(hipStream_t st, const float* src_xy, const float* dst_xy, const int* moff, int n_segments,
                        int m_cap, int model, double thr, int max_iters, double confidence, double* H, int* found,
                        unsigned char* mask_out);
+// fundamental.hip: findFundamentalMat(FM_RANSAC) on the host; F is 3x3 row-major, [dst;1]^T F [src;1] = 0.
+int find_fundamental_ransac(const float* src_xy, const float* dst_xy, int n, double thr, int max_iters,
+                            double confidence, double* F, unsigned char* mask_out);
+// fundamental_batch.hip: the same per segment, one workgroup each, no scratch; F is [n_segments][9].
+void launch_fundamental_seg(hipStream_t st, const float* src_xy, const float* dst_xy, const int* moff, int n_segments,
+                            int m_cap, double thr, int max_iters, double confidence, double* F, int* found,
+                            unsigned char* mask_out);
 // sift_selftest_math ops 8 / 9: out[i] = update_num_iters(confidence, (good[i] of n[i] pairs), 4, 2000)
 void launch_update_num_iters_selftest(hipStream_t st, double confidence, const float* good, const float* n, float* out,
                                       int count);

@@ -99,45 +99,48 @@ SIFT_HD bool get_subset(Rng& rng, const P2* s, const P2* d, int n, int* idx, P2*
   return false;
 }
 
-// Symmetric 9x9 eigen decomposition (cyclic Jacobi); returns the eigenvector
+// Symmetric N x N eigen decomposition (cyclic Jacobi); returns the eigenvector
 // of the smallest eigenvalue.  Every index is a compile-time constant once the
-// loops are unrolled, so on the device A and V live in registers.
-SIFT_HD void smallest_eigvec(double A[9][9], double v[9]) {
-  double V[9][9];
+// loops are unrolled, so on the device A and V live in registers.  N is deduced
+// from A: 9 for the DLT and the 8-point solve, 3 for the latter's rank-2 step
+// (fundamental_math.hpp); the statements are the same for every N.
+template <int N>
+SIFT_HD void smallest_eigvec(double A[N][N], double* v) {
+  double V[N][N];
 #pragma unroll
-  for (int i = 0; i < 9; ++i)
+  for (int i = 0; i < N; ++i)
 #pragma unroll
-    for (int j = 0; j < 9; ++j) V[i][j] = i == j;
+    for (int j = 0; j < N; ++j) V[i][j] = i == j;
 #pragma unroll 1
   for (int sweep = 0; sweep < 60; ++sweep) {
     double off = 0;
 #pragma unroll
-    for (int i = 0; i < 9; ++i)
+    for (int i = 0; i < N; ++i)
 #pragma unroll
-      for (int j = i + 1; j < 9; ++j) off += A[i][j] * A[i][j];
+      for (int j = i + 1; j < N; ++j) off += A[i][j] * A[i][j];
     if (off < 1e-300) break;
 #pragma unroll
-    for (int p = 0; p < 9; ++p)
+    for (int p = 0; p < N; ++p)
 #pragma unroll
-      for (int q = p + 1; q < 9; ++q) {
+      for (int q = p + 1; q < N; ++q) {
         if (fabs(A[p][q]) < 1e-300) continue;
         const double th = (A[q][q] - A[p][p]) / (2 * A[p][q]);
         const double t = (th >= 0 ? 1 : -1) / (fabs(th) + sqrt(th * th + 1));
         const double c = 1 / sqrt(t * t + 1), s = t * c;
 #pragma unroll
-        for (int k = 0; k < 9; ++k) {
+        for (int k = 0; k < N; ++k) {
           const double akp = A[k][p], akq = A[k][q];
           A[k][p] = c * akp - s * akq;
           A[k][q] = s * akp + c * akq;
         }
 #pragma unroll
-        for (int k = 0; k < 9; ++k) {
+        for (int k = 0; k < N; ++k) {
           const double apk = A[p][k], aqk = A[q][k];
           A[p][k] = c * apk - s * aqk;
           A[q][k] = s * apk + c * aqk;
         }
 #pragma unroll
-        for (int k = 0; k < 9; ++k) {
+        for (int k = 0; k < N; ++k) {
           const double vkp = V[k][p], vkq = V[k][q];
           V[k][p] = c * vkp - s * vkq;
           V[k][q] = s * vkp + c * vkq;
@@ -147,13 +150,13 @@ SIFT_HD void smallest_eigvec(double A[9][9], double v[9]) {
   // the first smallest diagonal entry's column, picked without a run-time index
   double least = A[0][0];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) v[k] = V[k][0];
+  for (int k = 0; k < N; ++k) v[k] = V[k][0];
 #pragma unroll
-  for (int i = 1; i < 9; ++i)
+  for (int i = 1; i < N; ++i)
     if (A[i][i] < least) {
       least = A[i][i];
 #pragma unroll
-      for (int k = 0; k < 9; ++k) v[k] = V[k][i];
+      for (int k = 0; k < N; ++k) v[k] = V[k][i];
     }
 }
 

@@ -345,4 +345,17 @@ inline AffineHost affine_host_layout(Carver& a, int n_segments, int m_cap) {
           a.take<unsigned char>((size_t)m_cap)};
 }
 
+// ---- fundamental matrix estimation (fundamental_batch.hip) ----
+// sift_find_fundamental_segmented_device: a round is kFundRound hypotheses, one
+// normalised 8-point solve per thread of the segment's workgroup.  A round's
+// subsets (8 rows each) and inlier counts live in LDS beside the refit's 64 x 45
+// terms (33 KB in all), the hypotheses in registers, so the device form
+// carves nothing from the block.  256 by the A/B of
+// profiles/fundamental_batch_ab.txt (64, 128, 256).
+constexpr int kFundRound = 256;
+
+// sift_find_fundamental_segmented stages what sift_estimate_affine_segmented
+// stages (pairs, offsets, nine doubles and a flag per segment, the mask):
+// affine_host_layout is its layout too.
+
 }  // namespace sift

@@ -38,6 +38,7 @@ SIFT_FLAG_FAST, SIFT_FLAG_PROFILE, SIFT_FLAG_VERBOSE, SIFT_FLAG_NO_GRAPH = 0x1, 
 N_SCALES, N_DOG, DESC_LEN = 5, 4, 128
 HOMOGRAPHY_ROUND = 64  # hypotheses per round of the segmented homography (scratch.hpp kHomogRound)
 AFFINE_ROUND = 128  # hypotheses per round of the segmented affine / similarity estimate (scratch.hpp kAffineRound)
+FUND_ROUND = 256  # hypotheses per round of the segmented fundamental-matrix estimate (scratch.hpp kFundRound)
 # sift_estimate_affine[_segmented[_device]]: the motion model
 SIFT_MODEL_AFFINE, SIFT_MODEL_SIMILARITY = 0, 1
 # sift_cross_match_segmented_device's metric: the distance and the type of the descriptor rows
@@ -173,6 +174,12 @@ def lib():
                                                            ctypes.c_double, vp, vp, vp]),
             "sift_estimate_affine_segmented": (ip, [vp, fp, fp, pint, ip, ip, ip, ctypes.c_double, ip,
                                                     ctypes.c_double, ctypes.POINTER(ctypes.c_double), pint, vp]),
+            "sift_find_fundamental": (ip, [fp, fp, ip, ctypes.c_double, ip, ctypes.c_double,
+                                           ctypes.POINTER(ctypes.c_double), vp]),
+            "sift_find_fundamental_segmented_device": (ip, [vp, vp, vp, vp, ip, ip, ctypes.c_double, ip,
+                                                            ctypes.c_double, vp, vp, vp]),
+            "sift_find_fundamental_segmented": (ip, [vp, fp, fp, pint, ip, ip, ctypes.c_double, ip, ctypes.c_double,
+                                                     ctypes.POINTER(ctypes.c_double), pint, vp]),
             "sift_multi_shard": (ip, [ip, ip, ip, pint, pint]),
             "sift_multi_merge_offsets": (ip, [ctypes.POINTER(pint), pint, ip, pint]),
             "sift_multi_create": (ip, [pint, ip, ip, ip, ip, ctypes.c_uint, ip, ip, ip, ctypes.POINTER(vp)]),
@@ -199,7 +206,9 @@ def lib():
                     "sift_knn_match_window_segmented_device", "sift_knn_match_window_segmented",
                     "sift_set_upsample", "sift_upsample2x", "sift_upsample2x_device",
                     "sift_warp_perspective_segmented_device", "sift_warp_perspective", "sift_estimate_affine",
-                    "sift_estimate_affine_segmented_device", "sift_estimate_affine_segmented"}  # absent from older builds (A/B runs against a saved library)
+                    "sift_estimate_affine_segmented_device", "sift_estimate_affine_segmented",
+                    "sift_find_fundamental", "sift_find_fundamental_segmented_device",
+                    "sift_find_fundamental_segmented"}  # absent from older builds (A/B runs against a saved library)
         for name, (res, args) in sigs.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -1018,6 +1027,46 @@ class Context:
         return [(H[b, :6].reshape(2, 3).copy() if found[b] else None, mask[o[b]:max(o[b], o[b + 1])].copy())
                 for b in range(nseg)]
 
+    # ---- a whole batch: fundamental matrix per segment of the same pairs ---
+    def find_fundamental_segmented_device(self, src_xy_ptr: int, dst_xy_ptr: int, m_offsets_ptr: int,
+                                          n_segments: int, m_cap: int, F_ptr: int, found_ptr: int,
+                                          mask_ptr: int | None = None, ransacReprojThreshold: float = 3.0,
+                                          maxIters: int = 1000, confidence: float = 0.99):
+        """Device-pointer form (no sync) of findFundamentalMat(FM_RANSAC) for every
+        segment [m_offsets[b], m_offsets[b+1]) of ratio_matches_device's point
+        pairs: F_ptr [n_segments][9] float64 ([dst;1]^T F [src;1] = 0), found_ptr
+        [n_segments] int32, mask_ptr [m_cap] uint8 or None."""
+        vp = lambda p: ctypes.c_void_p(p or None)  # noqa: E731
+        self._check("sift_find_fundamental_segmented_device",
+                    self._L.sift_find_fundamental_segmented_device(
+                        self.h, vp(src_xy_ptr), vp(dst_xy_ptr), vp(m_offsets_ptr), n_segments, m_cap,
+                        float(ransacReprojThreshold), int(maxIters), float(confidence), vp(F_ptr), vp(found_ptr),
+                        vp(mask_ptr)))
+
+    def findFundamentalBatch(self, src, dst, m_offsets, ransacReprojThreshold: float = 3.0, maxIters: int = 1000,
+                             confidence: float = 0.99):
+        """findFundamentalMat(FM_RANSAC) for every segment at once (host arrays): a
+        list of (F 3x3 float64 or None, inlier mask uint8[segment's pairs]) per
+        segment, offsets clamped to the number of pairs."""
+        s = np.ascontiguousarray(src, np.float32).reshape(-1, 2)
+        d = np.ascontiguousarray(dst, np.float32).reshape(-1, 2)
+        mo = np.ascontiguousarray(m_offsets, np.int32)
+        if len(s) != len(d) or mo.ndim != 1 or len(mo) < 1:
+            raise ValueError("src / dst must be [n, 2] and m_offsets n_segments + 1 entries")
+        nseg, n = len(mo) - 1, len(s)
+        F = np.zeros((nseg, 9), np.float64)
+        found = np.zeros(nseg, np.int32)
+        mask = np.zeros(n, np.uint8)
+        pint = ctypes.POINTER(ctypes.c_int)
+        self._check("sift_find_fundamental_segmented",
+                    self._L.sift_find_fundamental_segmented(
+                        self.h, _fp(s), _fp(d), mo.ctypes.data_as(pint), nseg, n, float(ransacReprojThreshold),
+                        int(maxIters), float(confidence), F.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                        found.ctypes.data_as(pint), mask.ctypes.data))
+        o = np.clip(mo.astype(np.int64), 0, n)
+        return [(F[b].reshape(3, 3).copy() if found[b] else None, mask[o[b]:max(o[b], o[b + 1])].copy())
+                for b in range(nseg)]
+
     # ---- device batch API ------------------------------------------------
     def synth_images(self, out_ptr: int, batch: int, rows: int, cols: int, row_stride: int,
                      img_stride: int, seed_base: int = 0):
@@ -1504,6 +1553,23 @@ def estimateAffinePartial2D(from_, to, ransacReprojThreshold: float = 3.0, maxIt
     """cv::estimateAffinePartial2D(from, to, RANSAC): rotation, uniform scale and translation,
     A = (a -b tx; b a ty) -> (A 2x3 float64 or None, inlier mask)."""
     return _estimate_affine(SIFT_MODEL_SIMILARITY, from_, to, ransacReprojThreshold, maxIters, confidence)
+
+
+def findFundamentalMat(src, dst, thr: float = 3.0, max_iters: int = 1000, confidence: float = 0.99):
+    """cv::findFundamentalMat(points1, points2, FM_RANSAC, thr, confidence, max_iters) -> (F 3x3 float64
+    or None, inlier mask), [dst;1]^T F [src;1] = 0.  Host code in the library (fundamental.hip): the
+    normalised 8-point solve inside RANSAC and again over the inliers (include/sift_hip.h has the rule)."""
+    s = np.ascontiguousarray(src, np.float32).reshape(-1, 2)
+    d = np.ascontiguousarray(dst, np.float32).reshape(-1, 2)
+    if len(s) != len(d):
+        raise ValueError("point counts differ")
+    F = np.zeros(9, np.float64)
+    m = np.zeros(max(len(s), 1), np.uint8)
+    rc = lib().sift_find_fundamental(_fp(s), _fp(d), len(s), float(thr), int(max_iters), float(confidence),
+                                     F.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), m.ctypes.data)
+    if rc != SIFT_OK:
+        return None, np.zeros(len(s), np.uint8)
+    return F.reshape(3, 3), m[:len(s)]
 
 
 WARP_INVERSE_MAP = 16  # cv::WARP_INVERSE_MAP

@@ -1097,6 +1097,65 @@ int sift_find_fundamental_segmented(sift_ctx* ctx, const float* src_xy, const fl
                                     int n_segments, int m_cap, double ransac_thresh, int max_iters, double confidence,
                                     double* F, int* found, unsigned char* inlier_mask /* may be NULL */);
 
+/* ---- matching along epipolar lines (match_epipolar.hip) --------------------- */
+/* Guided matching for the third model (Hartley & Zisserman, Algorithm 11.4):
+ * the windowed matcher above, with its contract word for word -- segments and
+ * clamping, d_t_offsets == NULL for a shared train set, local indices, k of 1
+ * or 2, ascending (distance, local train index), idx -1 / dist +inf fill, rows
+ * outside the query range untouched, n_segments == 0 or q_cap == 0 SIFT_OK with
+ * nothing enqueued, SIFT_METRIC_L1_F32 / _L1_U8 / _L2SQR_U8 (SIFT_METRIC_L2SQR_F32
+ * is rejected), distances the dense matchers' own bit for bit, context stream,
+ * no synchronisation, no host read of an offset or a model -- and a second gate.
+ * Train row t with keypoint (X, Y) is admissible for query row q with keypoint
+ * (x, y) of segment b iff both tests hold:
+ *   Window: fabsf(X - x) <= radius && fabsf(Y - y) <= radius, in float -- the
+ *   windowed matcher's test around the query's OWN position, the disparity bound
+ *   of a stereo search.  radius = +inf admits every row with comparable
+ *   coordinates; a NaN coordinate on either side makes the row inadmissible,
+ *   always.
+ *   Band: skipped when d_F == NULL, or when d_found != NULL and d_found[b] == 0
+ *   (the segment has no model: the window alone gates it).  Otherwise the pair
+ *   must be an inlier of F = d_F + 9 b by sift_find_fundamental's own test at the
+ *   limit t = (float)(band * band), the product formed in double: the nine
+ *   coefficients cast to float, unfused float arithmetic left to right, both
+ *   squared point-to-epipolar-line distances d_dst^2 s_dst and d_src^2 s_src
+ *   <= t, with src = query and dst = train, the convention
+ *   sift_find_fundamental* writes.  It is one function, compiled for the
+ *   estimate and for this matcher (fmath::is_inlier, csrc/fundamental_math.hpp).
+ *   A NaN error (a query at the epipole, a non-finite F) is inadmissible;
+ *   band = +inf admits every pair whose two errors are not NaN, band = 0 only
+ *   exact zeros.
+ * d_F is [n_segments][9] doubles and d_found [n_segments] ints exactly as
+ * sift_find_fundamental_segmented_device writes them, so pair b's model gates
+ * pair b's next match in stream order with no host value, and d_idx / d_dist
+ * [q_cap][k] go to sift_ratio_matches_device and the next estimate unchanged.
+ * With d_F == NULL the output equals sift_knn_match_window_segmented_device(...,
+ * d_H = NULL, ...) byte for byte at every radius; with radius = +inf as well and
+ * finite coordinates it equals the dense call of the metric byte for byte.
+ * rows, cols: the train images' extent, a hint that shapes the search grid; no
+ * result depends on it.
+ * SIFT_E_INVALID: the windowed matcher's list (NULL context, NULL required
+ * buffer -- both keypoint arrays are required --, unknown metric, k outside
+ * {1, 2}, radius negative or NaN, rows or cols < 1, unaligned rows), and band
+ * negative or NaN.
+ * Out of scope: a gated reverse pass or a gated cross-check (they would need
+ * the transposed model and the inverse window), SIFT_METRIC_L2SQR_F32, and a
+ * one-sided (train-image-only) distance. */
+int sift_knn_match_epipolar_segmented_device(sift_ctx* ctx, int metric, const void* d_query,
+                                             const sift_keypoint* d_q_kpts, const int* d_q_offsets, int n_segments,
+                                             int q_cap, const void* d_train, const sift_keypoint* d_t_kpts,
+                                             const int* d_t_offsets /* NULL = shared */, int t_cap,
+                                             const double* d_F /* may be NULL */, const int* d_found /* may be NULL */,
+                                             double band, float radius, int rows, int cols, int k, int* d_idx,
+                                             float* d_dist);
+/* Host buffers (synchronous); query and q_kpts have q_cap rows, train and
+ * t_kpts t_cap rows, F n_segments x 9 doubles, found n_segments ints: */
+int sift_knn_match_epipolar_segmented(sift_ctx* ctx, int metric, const void* query, const sift_keypoint* q_kpts,
+                                      const int* q_offsets, int n_segments, int q_cap, const void* train,
+                                      const sift_keypoint* t_kpts, const int* t_offsets /* NULL = shared */, int t_cap,
+                                      const double* F /* may be NULL */, const int* found /* may be NULL */,
+                                      double band, float radius, int rows, int cols, int k, int* idx, float* dist);
+
 /* ---- self-test ------------------------------------------------------------ */
 /* Evaluates one device arithmetic helper element-wise on host arrays (n
  * values), for bit-exact checks of the GPU math against the CPU oracle:

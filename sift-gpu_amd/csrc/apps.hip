@@ -1,13 +1,13 @@
 // apps.hip -- the application stages behind the C ABI (include/sift_hip.h):
 // the L1 kNN matcher, the byte quantiser, the four segmented matchers (float
-// L1, byte L1, byte squared L2, float squared L2), the windowed matcher, the ratio test with
+// L1, byte L1, byte squared L2, float squared L2), the windowed and the epipolar matcher, the ratio test with
 // point pairs, the cross-check stage with its one-call form, the BGR8 front
 // end and the doubled image, each in a device and a host form, the one-pair
 // homography wrappers, the segmented homography and corner transform, the
 // affine / similarity estimate and the fundamental matrix (each one pair set
 // and segmented; fundamental.hip, fundamental_batch.hip), and the
 // perspective warp of a batch.  Host code only; the kernels live in match.hip,
-// match_u8.hip, match_l2_u8.hip, match_l2_f32.hip, match_window.hip, cross_check.hip,
+// match_u8.hip, match_l2_u8.hip, match_l2_f32.hip, match_window.hip, match_epipolar.hip, cross_check.hip,
 // frontend.hip, upsample.hip, homography_batch.hip, affine_batch.hip and warp.hip (the one-pair
 // homography and affine estimate are host code in homography.hip and affine.hip).  The segmented matchers are one path, written once as
 // function templates over a metric tag (MatchL1F32, MatchL1U8, MatchL2SqrU8, MatchL2SqrF32);
@@ -323,6 +323,36 @@ int window_device(sift_ctx* c, int metric, const void* q, const sift_keypoint* q
   {
     StageScope sc(c, ST_MATCH_WINDOW);  // the work depends on offsets and positions only the device knows
     launch_knn_window(c->stream, A);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
+// ---- matching along epipolar lines: the windowed matcher gated by the band of F as well (match_epipolar.hip) ----
+int check_epipolar(sift_ctx* c, int metric, const void* query, const sift_keypoint* q_kpts, const int* q_offsets,
+                   int n_segments, int q_cap, const void* train, const sift_keypoint* t_kpts, int t_cap, double band,
+                   float radius, int rows, int cols, int k, const int* idx, const float* dist) {
+  if (!c) return SIFT_E_INVALID;
+  if (!(band >= 0)) return fail(c, SIFT_E_INVALID, "band must be 0 or positive (+inf: no gate)");
+  return check_window(c, metric, query, q_kpts, q_offsets, n_segments, q_cap, train, t_kpts, t_cap, radius, rows, cols,
+                      k, idx, dist);
+}
+
+// As window_device; F in H's place, the limit as the estimate forms its own.
+int epipolar_device(sift_ctx* c, int metric, const void* q, const sift_keypoint* q_kpts, const int* qoff,
+                    int n_segments, int q_cap, const void* t, const sift_keypoint* t_kpts, const int* toff, int t_cap,
+                    const double* F, const int* found, double band, float radius, int k, int* idx, float* dist,
+                    WindowGrid G, WindowParts P) {
+  const EpipolarArgs A{{metric, q, q_kpts, qoff, n_segments, q_cap, t, t_kpts, toff, t_cap, F, found, radius,
+                        G.nx, G.ny, G.inv_cell, P.cell_end, P.cell_rows, dev(P.cell_xy), k, idx, dist},
+                       (float)(band * band)};
+  {
+    StageScope sc(c, ST_WINDOW_BIN, 0, 2.0 * (sizeof(sift_keypoint) + 12.0) * A.W.t_cap);
+    HIP_TRY(c, launch_window_bin(c->stream, A.W));
+  }
+  {
+    StageScope sc(c, ST_MATCH_EPIPOLAR);  // the work depends on offsets, positions and models only the device knows
+    launch_knn_epipolar(c->stream, A);
   }
   HIP_TRY(c, hipGetLastError());
   return SIFT_OK;
@@ -777,6 +807,64 @@ int sift_knn_match_window_segmented(sift_ctx* c, int metric, const void* query, 
     HIP_TRY(c, hipMemcpyAsync(S.found, found, (size_t)n_segments * sizeof(int), hipMemcpyHostToDevice, c->stream));
   if ((rc = window_device(c, metric, S.query, S.q_kpts, S.q_off, n_segments, q_cap, S.train, S.t_kpts, S.t_off, t_cap,
                           S.H, S.found, radius, k, S.idx, S.dist, G, S.win)))
+    return rc;
+  return copy_back_live_rows(c, q_offsets, n_segments, q_cap, k, idx, dist, S.idx, S.dist);
+}
+
+int sift_knn_match_epipolar_segmented_device(sift_ctx* c, int metric, const void* d_query,
+                                             const sift_keypoint* d_q_kpts, const int* d_q_offsets, int n_segments,
+                                             int q_cap, const void* d_train, const sift_keypoint* d_t_kpts,
+                                             const int* d_t_offsets, int t_cap, const double* d_F, const int* d_found,
+                                             double band, float radius, int rows, int cols, int k, int* d_idx,
+                                             float* d_dist) {
+  int rc = check_epipolar(c, metric, d_query, d_q_kpts, d_q_offsets, n_segments, q_cap, d_train, d_t_kpts, t_cap, band,
+                          radius, rows, cols, k, d_idx, d_dist);
+  if (rc || n_segments == 0 || q_cap == 0) return rc;
+  if (!aligned16(d_query, d_train)) return fail(c, SIFT_E_INVALID, kRowsUnaligned);
+  (void)hipSetDevice(c->device);
+  const int n_grids = d_t_offsets ? n_segments : 1;
+  const WindowGrid G = epipolar_grid(radius, d_F ? band : INFINITY, rows, cols, t_cap, n_grids);
+  WindowParts P;
+  if ((rc = carve(c, &P, [&](Carver& a) { return window_layout(a, n_grids, G.nx * G.ny, t_cap); }))) return rc;
+  return epipolar_device(c, metric, d_query, d_q_kpts, d_q_offsets, n_segments, q_cap, d_train, d_t_kpts, d_t_offsets,
+                         t_cap, d_F, d_found, band, radius, k, d_idx, d_dist, G, P);
+}
+
+int sift_knn_match_epipolar_segmented(sift_ctx* c, int metric, const void* query, const sift_keypoint* q_kpts,
+                                      const int* q_offsets, int n_segments, int q_cap, const void* train,
+                                      const sift_keypoint* t_kpts, const int* t_offsets, int t_cap, const double* F,
+                                      const int* found, double band, float radius, int rows, int cols, int k, int* idx,
+                                      float* dist) {
+  int rc = check_epipolar(c, metric, query, q_kpts, q_offsets, n_segments, q_cap, train, t_kpts, t_cap, band, radius,
+                          rows, cols, k, idx, dist);
+  if (rc || n_segments == 0 || q_cap == 0) return rc;
+  (void)hipSetDevice(c->device);
+  const int n_grids = t_offsets ? n_segments : 1;
+  const WindowGrid G = epipolar_grid(radius, F ? band : INFINITY, rows, cols, t_cap, n_grids);
+  const size_t row = metric_row_bytes(metric);
+  EpipolarHost S;
+  if ((rc = carve(c, &S, [&](Carver& a) {
+         return epipolar_host_layout(a, n_segments, q_cap, t_cap, row, t_offsets != nullptr, F != nullptr,
+                                     found != nullptr, k, n_grids, G.nx * G.ny);
+       })))
+    return rc;
+  const size_t ob = (size_t)(n_segments + 1) * sizeof(int);
+  HIP_TRY(c, hipMemcpyAsync(S.query, query, q_cap * row, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.q_kpts, q_kpts, (size_t)q_cap * sizeof(sift_keypoint), hipMemcpyHostToDevice,
+                            c->stream));
+  if (t_cap) {
+    HIP_TRY(c, hipMemcpyAsync(S.train, train, t_cap * row, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(S.t_kpts, t_kpts, (size_t)t_cap * sizeof(sift_keypoint), hipMemcpyHostToDevice,
+                              c->stream));
+  }
+  HIP_TRY(c, hipMemcpyAsync(S.q_off, q_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  if (S.t_off) HIP_TRY(c, hipMemcpyAsync(S.t_off, t_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  if (S.F)
+    HIP_TRY(c, hipMemcpyAsync(S.F, F, (size_t)n_segments * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (S.found)
+    HIP_TRY(c, hipMemcpyAsync(S.found, found, (size_t)n_segments * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if ((rc = epipolar_device(c, metric, S.query, S.q_kpts, S.q_off, n_segments, q_cap, S.train, S.t_kpts, S.t_off,
+                            t_cap, S.F, S.found, band, radius, k, S.idx, S.dist, G, S.win)))
     return rc;
   return copy_back_live_rows(c, q_offsets, n_segments, q_cap, k, idx, dist, S.idx, S.dist);
 }

@@ -403,6 +403,17 @@ struct WindowArgs {
 };
 hipError_t launch_window_bin(hipStream_t st, const WindowArgs& A);
 void launch_knn_window(hipStream_t st, const WindowArgs& A);
+// match_epipolar.hip: the segmented matcher gated by the window around the
+// query's own position and by the epipolar band of the segment's fundamental
+// matrix.  W is the windowed matcher's argument block with the same binning
+// (launch_window_bin) and W.H = F, [nseg][9] doubles as
+// sift_find_fundamental_segmented_device writes them (nullptr: the window
+// alone); limit is (float)(band * band), the estimate's own inlier limit.
+struct EpipolarArgs {
+  WindowArgs W;
+  float limit;
+};
+void launch_knn_epipolar(hipStream_t st, const EpipolarArgs& A);
 // pyramid_pc.hip (SIFT_FLAG_FAST): octave o's five planes by the separable
 // form, plus octave o+1's plane 0 when pyramid_fuses_decimation(L, o + 1)
 // (else decimate first), from a producer wave and three consumer waves

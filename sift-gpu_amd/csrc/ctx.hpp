@@ -63,7 +63,8 @@ class Buf {
   X(ST_COMPUTE_PREP, "compute_prep") X(ST_WINDOW_BIN, "match_window_bin")                              \
   X(ST_MATCH_WINDOW, "match_window_segmented") X(ST_UPSAMPLE, "upsample2x")                \
   X(ST_WARP, "warp") X(ST_AFFINE_SEG, "affine_segmented")                                  \
-  X(ST_MATCH_L2_F32, "match_l2sqr_f32_segmented") X(ST_FUND_SEG, "fundamental_segmented")
+  X(ST_MATCH_L2_F32, "match_l2sqr_f32_segmented") X(ST_FUND_SEG, "fundamental_segmented") \
+  X(ST_MATCH_EPIPOLAR, "match_epipolar")
 enum Stage {
 #define X(id, name) id,
   SIFT_STAGES(X)

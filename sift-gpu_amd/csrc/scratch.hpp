@@ -1,12 +1,12 @@
-// scratch.hpp -- how the matcher, byte-matcher, windowed-matcher, cross-check, front-end, segmented-homography and
+// scratch.hpp -- how the matcher, byte-matcher, windowed-matcher, epipolar-matcher, cross-check, front-end, segmented-homography and
 // segmented-affine entry points divide the context's one scratch block (sift_ctx::d_match).  Each
 // layout is described once, as a function of a Carver, and run twice: on a null
 // base to measure the block, then on the block itself.  The four segmented
 // matchers share one host and one cross-match layout, templates over a metric
 // tag (L1F32, L1U8, L2SqrU8, L2SqrF32).  Plain host C++ (no HIP
 // include), so that tests/cpp/scratch_layout.cpp, match_u8_layout.cpp,
-// match_l2_u8_layout.cpp, match_l2_f32_layout.cpp, cross_check_layout.cpp, homography_layout.cpp, match_window_layout.cpp and
-// affine_layout.cpp check every layout without a GPU.
+// match_l2_u8_layout.cpp, match_l2_f32_layout.cpp, cross_check_layout.cpp, homography_layout.cpp, match_window_layout.cpp,
+// match_epipolar_layout.cpp and affine_layout.cpp check every layout without a GPU.
 #pragma once
 
 #include <math.h>
@@ -283,6 +283,45 @@ inline WindowHost window_host_layout(Carver& a, int n_segments, int q_cap, int t
           a.take<sift_keypoint>((size_t)q_cap), a.take<sift_keypoint>(at_least_one(t_cap)),
           a.take<int>((size_t)q_cap * k), a.take<float>((size_t)q_cap * k), a.take<int>((size_t)n_segments + 1),
           a.take_if<int>(has_t_off, (size_t)n_segments + 1), a.take_if<double>(has_H, (size_t)n_segments * 9),
+          a.take_if<int>(has_found, (size_t)n_segments), window_layout(a, n_grids, n_cells, t_cap)};
+}
+
+// ---- matching along epipolar lines (match_epipolar.hip) ----
+// The search grid of sift_knn_match_epipolar_segmented_device, under
+// window_grid's cell cap: square cells of side kEpipolarCellScale x
+// max(min(radius, band), 1 px), grown until one grid fits the cap.  The walk
+// visits the cells of a strip 2 band wide inside a window 2 radius wide, so the
+// narrower of the two sets the useful cell side; the scale is the A/B of
+// profiles/match_epipolar_ab.txt.  Both +inf is one cell.  No result depends on
+// the grid's shape.
+#ifndef SIFT_EPIPOLAR_CELL_SCALE
+#define SIFT_EPIPOLAR_CELL_SCALE 1
+#endif
+constexpr double kEpipolarCellScale = SIFT_EPIPOLAR_CELL_SCALE;
+inline WindowGrid epipolar_grid(float radius, double band, int rows, int cols, int t_cap, int n_grids) {
+  const double cap = window_cell_cap(t_cap, n_grids);
+  double cell = band < (double)radius ? band : (double)radius;
+  cell = (cell > 1. ? cell : 1.) * kEpipolarCellScale;
+  if (!(cell <= 2e9)) return {1, 1, 0.f};  // wider than any extent, +inf included
+  for (;; cell *= 1.125) {
+    const double nx = ceil(cols / cell), ny = ceil(rows / cell);
+    if (nx * ny <= cap) return {(int)nx, (int)ny, (float)(1. / cell)};
+  }
+}
+
+// sift_knn_match_epipolar_segmented_device carves window_layout.
+// sift_knn_match_epipolar_segmented: the windowed matcher's host layout with F
+// ([n_segments][9] doubles) in H's place.
+struct EpipolarHost {
+  uint8_t *query, *train; sift_keypoint *q_kpts, *t_kpts; int* idx; float* dist; int *q_off, *t_off; double* F;
+  int* found; WindowParts win;
+};
+inline EpipolarHost epipolar_host_layout(Carver& a, int n_segments, int q_cap, int t_cap, size_t row_bytes,
+                                         bool has_t_off, bool has_F, bool has_found, int k, int n_grids, int n_cells) {
+  return {a.take<uint8_t>((size_t)q_cap * row_bytes), a.take<uint8_t>(at_least_one(t_cap) * row_bytes),
+          a.take<sift_keypoint>((size_t)q_cap), a.take<sift_keypoint>(at_least_one(t_cap)),
+          a.take<int>((size_t)q_cap * k), a.take<float>((size_t)q_cap * k), a.take<int>((size_t)n_segments + 1),
+          a.take_if<int>(has_t_off, (size_t)n_segments + 1), a.take_if<double>(has_F, (size_t)n_segments * 9),
           a.take_if<int>(has_found, (size_t)n_segments), window_layout(a, n_grids, n_cells, t_cap)};
 }
 

@@ -163,6 +163,10 @@ def lib():
                                                             ctypes.c_float, ip, ip, ip, vp, vp]),
             "sift_knn_match_window_segmented": (ip, [vp, ip, vp, vp, pint, ip, ip, vp, vp, pint, ip, vp, pint,
                                                      ctypes.c_float, ip, ip, ip, pint, fp]),
+            "sift_knn_match_epipolar_segmented_device": (ip, [vp, ip, vp, vp, vp, ip, ip, vp, vp, vp, ip, vp, vp,
+                                                              ctypes.c_double, ctypes.c_float, ip, ip, ip, vp, vp]),
+            "sift_knn_match_epipolar_segmented": (ip, [vp, ip, vp, vp, pint, ip, ip, vp, vp, pint, ip, vp, pint,
+                                                       ctypes.c_double, ctypes.c_float, ip, ip, ip, pint, fp]),
             "sift_find_homography_segmented_device": (ip, [vp, vp, vp, vp, ip, ip, ctypes.c_double, ip,
                                                            ctypes.c_double, vp, vp, vp]),
             "sift_find_homography_segmented": (ip, [vp, fp, fp, pint, ip, ip, ctypes.c_double, ip, ctypes.c_double,
@@ -208,7 +212,8 @@ def lib():
                     "sift_warp_perspective_segmented_device", "sift_warp_perspective", "sift_estimate_affine",
                     "sift_estimate_affine_segmented_device", "sift_estimate_affine_segmented",
                     "sift_find_fundamental", "sift_find_fundamental_segmented_device",
-                    "sift_find_fundamental_segmented"}  # absent from older builds (A/B runs against a saved library)
+                    "sift_find_fundamental_segmented", "sift_knn_match_epipolar_segmented_device",
+                    "sift_knn_match_epipolar_segmented"}  # absent from older builds (A/B runs against a saved library)
         for name, (res, args) in sigs.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -852,6 +857,67 @@ class Context:
                         _fp(dist)))
         return idx, dist
 
+    # ---- matching along epipolar lines (kNN gated by the batch's fundamental matrices) ----
+    def knn_match_epipolar_segmented_device(self, metric: int, query_ptr: int, q_kpts_ptr: int, q_offsets_ptr: int,
+                                            n_segments: int, q_cap: int, train_ptr: int, t_kpts_ptr: int,
+                                            t_offsets_ptr: int | None, t_cap: int, F_ptr: int | None,
+                                            found_ptr: int | None, band: float, radius: float, rows: int, cols: int,
+                                            k: int, idx_ptr: int, dist_ptr: int):
+        """Device-pointer form (no sync) of the epipolar matcher: the windowed
+        matcher around the query keypoint's own position (`radius`, a closed square,
+        float compare; +inf: no window), where a train row is a candidate only if
+        the pair is also an inlier of the segment's fundamental matrix at `band`
+        pixels -- find_fundamental's own float test, both point-to-epipolar-line
+        distances <= band (src = query, dst = train).  F [n_segments][9] float64
+        and found [n_segments] int32 as find_fundamental_segmented_device writes
+        them; F_ptr None, or found[b] == 0: the window alone.  rows, cols: the train
+        images' extent, a hint for the search grid only.  Same outputs and contract
+        as knn_match_window_segmented_device otherwise."""
+        vp = lambda p: ctypes.c_void_p(p or None)  # noqa: E731
+        self._check("sift_knn_match_epipolar_segmented_device",
+                    self._L.sift_knn_match_epipolar_segmented_device(
+                        self.h, int(metric), vp(query_ptr), vp(q_kpts_ptr), vp(q_offsets_ptr), n_segments, q_cap,
+                        vp(train_ptr), vp(t_kpts_ptr), vp(t_offsets_ptr), t_cap, vp(F_ptr), vp(found_ptr),
+                        float(band), float(radius), rows, cols, k, vp(idx_ptr), vp(dist_ptr)))
+
+    def knnMatchEpipolarSegmented(self, metric: int, query: np.ndarray, q_kpts: np.ndarray, q_offsets,
+                                  train: np.ndarray, t_kpts: np.ndarray, t_offsets=None, F=None, found=None,
+                                  band: float = 3.0, radius: float = float("inf"), image_size=(1080, 1920),
+                                  k: int = 2):
+        """knn_match_epipolar_segmented_device on host arrays (synchronous): idx
+        int32, dist float32 [len(query), k].  query / train are float32 rows for
+        SIFT_METRIC_L1_F32 and uint8 rows otherwise; q_kpts / t_kpts are
+        KEYPOINT_DTYPE arrays, one per row; F is [n_segments, 9] (or [n_segments, 3,
+        3]) float64, found [n_segments] int32; image_size = (rows, cols)."""
+        if metric == SIFT_METRIC_L1_F32:
+            q = np.ascontiguousarray(query, np.float32).reshape(-1, DESC_LEN)
+            t = np.ascontiguousarray(train, np.float32).reshape(-1, DESC_LEN)
+        else:
+            q, t = self._u8_rows(query), self._u8_rows(train)
+        qk, tk = np.ascontiguousarray(q_kpts, KEYPOINT_DTYPE), np.ascontiguousarray(t_kpts, KEYPOINT_DTYPE)
+        if len(qk) != len(q) or len(tk) != len(t):
+            raise ValueError("one keypoint per descriptor row")
+        qo = np.ascontiguousarray(q_offsets, np.int32)
+        to = None if t_offsets is None else np.ascontiguousarray(t_offsets, np.int32)
+        if qo.ndim != 1 or len(qo) < 1 or (to is not None and to.shape != qo.shape):
+            raise ValueError("offsets must be 1-D, n_segments + 1 entries each")
+        n = len(qo) - 1
+        Fh = None if F is None else np.ascontiguousarray(F, np.float64).reshape(-1, 9)
+        fh = None if found is None else np.ascontiguousarray(found, np.int32)
+        if (Fh is not None and len(Fh) != n) or (fh is not None and fh.shape != (n,)):
+            raise ValueError("F is [n_segments, 9], found [n_segments]")
+        pint = ctypes.POINTER(ctypes.c_int)
+        idx = np.full((len(q), k), -1, np.int32)
+        dist = np.full((len(q), k), np.inf, np.float32)
+        self._check("sift_knn_match_epipolar_segmented",
+                    self._L.sift_knn_match_epipolar_segmented(
+                        self.h, int(metric), q.ctypes.data, qk.ctypes.data, qo.ctypes.data_as(pint), n, len(q),
+                        t.ctypes.data, tk.ctypes.data, None if to is None else to.ctypes.data_as(pint), len(t),
+                        None if Fh is None else Fh.ctypes.data, None if fh is None else fh.ctypes.data_as(pint),
+                        float(band), float(radius), int(image_size[0]), int(image_size[1]), k,
+                        idx.ctypes.data_as(pint), _fp(dist)))
+        return idx, dist
+
     # ---- cross-check (mutual nearest neighbours) for a whole batch ------------
     def cross_check_matches_device(self, idx_ptr: int, dist_ptr: int, fwd_k: int, q_offsets_ptr: int, n_segments: int,
                                    q_cap: int, ridx_ptr: int, rev_k: int, t_offsets_ptr: int, t_cap: int,
@@ -1464,6 +1530,39 @@ def window_match(query_desc, query_kpts, train_desc, train_kpts, radius, H=None,
     idx, dist = ctx.knnMatchWindowSegmented(metric, q, query_kpts, [0, len(q)], t, tk, None, radius,
                                             None if H is None else np.asarray(H, np.float64).reshape(1, 9), None,
                                             image_size, k)
+    return [[DMatch(i, int(idx[i, j]), 0, float(dist[i, j])) for j in range(k) if idx[i, j] >= 0]
+            for i in range(len(idx))]
+
+
+def epipolar_match(query_desc, query_kpts, train_desc, train_kpts, F, band: float = 3.0,
+                   radius: float = float("inf"), normType: int = NORM_L1, k: int = 2, image_size=None,
+                   ctx: Context | None = None):
+    """Guided matching along epipolar lines for one pair of descriptor sets:
+    `BFMatcher(normType).knnMatch(query, train, k, mask)` with the mask of F (3 x 3,
+    [train; 1]^T F [query; 1] = 0, as findFundamentalMat returns it).  Train row t
+    is a candidate for query row q only if both points lie within `band` pixels of
+    the other's epipolar line (find_fundamental's float32 inlier test at that
+    threshold) and, with a finite `radius`, |tx - qx| <= radius and |ty - qy| <=
+    radius (the disparity bound).  Per query a list of up to k DMatch, nearest
+    first.  The matcher is picked from the dtypes as BFMatcher.knnMatch picks it;
+    image_size = (rows, cols) of the train image only shapes the search grid.
+    F None: the window alone (window_match without a prior)."""
+    both_u8 = np.asarray(query_desc).dtype == np.uint8 and np.asarray(train_desc).dtype == np.uint8
+    if normType not in (NORM_L1, NORM_L2SQR):
+        raise ValueError("only NORM_L1 and NORM_L2SQR are implemented")
+    if normType == NORM_L2SQR and not both_u8:
+        raise ValueError("NORM_L2SQR takes two uint8 descriptor arrays")
+    metric = SIFT_METRIC_L2SQR_U8 if normType == NORM_L2SQR else SIFT_METRIC_L1_U8 if both_u8 else SIFT_METRIC_L1_F32
+    q = np.asarray(query_desc).reshape(-1, DESC_LEN)
+    t = np.asarray(train_desc).reshape(-1, DESC_LEN)
+    tk = np.ascontiguousarray(train_kpts, KEYPOINT_DTYPE)
+    if image_size is None:
+        ext = [tk[f][np.isfinite(tk[f])] for f in ("y", "x")]
+        image_size = tuple(int(min(max(float(e.max()) + 1, 1), 1 << 30)) if len(e) else 1 for e in ext)
+    ctx = ctx or _ctx(1, 1)
+    idx, dist = ctx.knnMatchEpipolarSegmented(metric, q, query_kpts, [0, len(q)], t, tk, None,
+                                              None if F is None else np.asarray(F, np.float64).reshape(1, 9), None,
+                                              band, radius, image_size, k)
     return [[DMatch(i, int(idx[i, j]), 0, float(dist[i, j])) for j in range(k) if idx[i, j] >= 0]
             for i in range(len(idx))]
 

@@ -1156,6 +1156,115 @@ int sift_knn_match_epipolar_segmented(sift_ctx* ctx, int metric, const void* que
                                       const double* F /* may be NULL */, const int* found /* may be NULL */,
                                       double band, float radius, int rows, int cols, int k, int* idx, float* dist);
 
+/* ---- relative pose and triangulation (pose.hip, pose_batch.hip) ------------- */
+/* `recoverPose(E, points1, points2, K, R, t, distanceThresh, mask,
+ * triangulatedPoints)` for a fundamental matrix and two calibrations: what a
+ * calibrated stereo rig or a moving camera does with the third model.  The
+ * convention is OpenCV's and sift_find_fundamental's: src is image 1, dst image
+ * 2, [dst; 1]^T F [src; 1] = 0, X_dst = R X_src + t, E ~ [t]x R.  F, K_src, K_dst
+ * are row-major 3x3 doubles; n point pairs as interleaved (x, y) floats in
+ * pixels; mask_in (n bytes, may be NULL = every row) says which rows vote --
+ * sift_find_fundamental's inlier mask --; distance_thresh is OpenCV's
+ * distanceThresh (50 in its samples; +inf allowed).  pose gets the twelve
+ * doubles of [R | t] row by row, the camera P_dst in normalised coordinates with
+ * |t| = 1; E (9, may be NULL) the essential matrix; mask_out (n bytes, may be
+ * NULL) the rows in front of both cameras; xyz (n x 3 doubles, may be NULL) their
+ * 3-D points in the src camera's frame; *n_good their number.  Host code, no
+ * context.  SIFT_E_INVALID with every output zeroed when there is no pose.
+ * The rule (csrc/pose_math.hpp), in double + - * / and sqrt only, no libm:
+ * 1. Calibration.  K may be any invertible matrix; K^-1 = adj(K) / det(K).  A
+ *    zero or non-finite determinant or a non-finite entry of the inverse: no
+ *    pose.  A pixel (x, y) becomes K^-1 (x, y, 1)^T divided by its third
+ *    component.
+ * 2. Essential matrix.  E0 = K_dst^T (F K_src).  The eigenpairs of E0^T E0 by
+ *    the homography's cyclic Jacobi at 3x3, ordered sigma_1^2 >= sigma_2^2 >=
+ *    sigma_3^2 (of equal values the one the Jacobi left first stays first).  A
+ *    non-finite sigma^2 or sigma_2^2 <= 0 -- a zero F, an E0 of rank 1 or of a
+ *    pure rotation where the arithmetic leaves an exact zero -- : no pose; one
+ *    that is degenerate only up to rounding goes on to the vote.  u1 = E0 v1 / sigma_1, u2 = E0 v2 / sigma_2, u3 =
+ *    u1 x u2; v3 is negated when det [v1 v2 v3] < 0.  The reported E is
+ *    ((sigma_1 + sigma_2) / 2) (u1 v1^T + u2 v2^T), the nearest essential matrix
+ *    (Hartley & Zisserman 9.6).
+ * 3. Candidates.  With W = [0 -1 0; 1 0 0; 0 0 1]: R1 = U W V^T, R2 = U W^T V^T,
+ *    t = u3, in cv::decomposeEssentialMat's order inside recoverPose: (R1, +t),
+ *    (R2, +t), (R1, -t), (R2, -t).  A non-finite entry: no pose.
+ * 4. Triangulation (cv::triangulatePoints, DLT).  For normalised points (x, y),
+ *    (X, Y) and cameras P_src, P_dst (3x4) the four rows x P_src[2] - P_src[0],
+ *    y P_src[2] - P_src[1], X P_dst[2] - P_dst[0], Y P_dst[2] - P_dst[1]; Q is the
+ *    eigenvector of the smallest eigenvalue of A^T A (the same Jacobi at 4x4),
+ *    the ten upper-triangle sums taken row 0 + row 1 + row 2 + row 3 and
+ *    mirrored.  Inside pose recovery P_src = [I | 0], P_dst = [R | t].
+ * 5. Cheirality.  A row is considered iff mask_in is NULL or its byte is
+ *    non-zero.  A considered row is good for a candidate iff, with Q /= Q[3],
+ *    0 < z < distance_thresh both for Q[2] and for (P_dst Q)[2], compared in
+ *    double: a NaN is never good.  The winner is the first candidate with the
+ *    largest count of good rows (OpenCV's >= chain); n_good is that count,
+ *    mask_out[row] = considered and good under the winner, xyz[row] the winner's
+ *    Q[0..2] for a good row and three zeros for any other.  There is a pose iff
+ *    the decomposition succeeded and n_good >= 1.  distance_thresh <= 0 or NaN:
+ *    no pose.
+ * The library's own rule, pinned bit for bit against tests/pose_oracle.py; not
+ * bit-compatible with OpenCV, which decomposes E by an SVD.  SIFT_E_INVALID also
+ * for a NULL F, K, pose or n_good, NULL points with n > 0, and n < 0. */
+int sift_recover_pose(const double* F, const double* K_src, const double* K_dst, const float* src_xy,
+                      const float* dst_xy, int n, const unsigned char* mask_in /* may be NULL */,
+                      double distance_thresh, double* pose /* [12], rows of [R | t] */, double* E /* [9], may be NULL */,
+                      unsigned char* mask_out /* [n], may be NULL */, double* xyz /* [n][3], may be NULL */,
+                      int* n_good);
+
+/* The same for every segment of a batch, on the device in stream order, with
+ * the contract of sift_find_fundamental_segmented_device: segment b's pairs are
+ * rows [clamp(m_offsets[b]), clamp(m_offsets[b+1])) of d_src_xy / d_dst_xy,
+ * clamped to m_cap, and each segment gets exactly what sift_recover_pose gives
+ * for its rows, bit for bit.  d_F [n_segments][9], d_found [n_segments] and
+ * d_mask_in [m_cap] (may be NULL) are taken exactly as
+ * sift_find_fundamental_segmented_device leaves d_F / d_found / d_inlier_mask,
+ * and are only read; d_found[b] == 0 means no pose.  k_per_segment 0: d_K_src
+ * and d_K_dst are one 3x3 each for all segments; 1: [n_segments][9].  d_pose is
+ * [n_segments][12], the camera P_dst that
+ * sift_triangulate_points_segmented_device takes; d_E [n_segments][9] (may be
+ * NULL); d_pose_found and d_n_good [n_segments] ints; d_mask_out [m_cap] bytes
+ * and d_xyz [m_cap][3] doubles by pair row (each may be NULL).  A segment with
+ * no pose gets pose and E of zeros, pose_found 0, n_good 0, and zero mask_out
+ * bytes and xyz rows.  Bytes and rows outside [clamp(m_offsets[0]),
+ * clamp(m_offsets[n_segments])) and rows of the per-segment outputs past
+ * n_segments are never written.
+ * Enqueued on the context stream, no synchronisation, no scratch, no host value
+ * read.  A NULL context: SIFT_E_INVALID.  n_segments == 0 or m_cap == 0:
+ * SIFT_OK, nothing enqueued.  A NULL required buffer, a negative count or
+ * k_per_segment outside {0, 1}: SIFT_E_INVALID (sift_last_error names it). */
+int sift_recover_pose_segmented_device(sift_ctx* ctx, const float* d_src_xy, const float* d_dst_xy,
+                                       const int* d_m_offsets, int n_segments, int m_cap, const double* d_F,
+                                       const int* d_found, const double* d_K_src, const double* d_K_dst,
+                                       int k_per_segment, const unsigned char* d_mask_in /* may be NULL */,
+                                       double distance_thresh, double* d_pose, double* d_E /* may be NULL */,
+                                       int* d_pose_found, int* d_n_good, unsigned char* d_mask_out /* may be NULL */,
+                                       double* d_xyz /* may be NULL */);
+/* Host buffers (synchronous); src_xy / dst_xy / mask_in / mask_out / xyz have
+ * m_cap rows: */
+int sift_recover_pose_segmented(sift_ctx* ctx, const float* src_xy, const float* dst_xy, const int* m_offsets,
+                                int n_segments, int m_cap, const double* F, const int* found, const double* K_src,
+                                const double* K_dst, int k_per_segment, const unsigned char* mask_in /* may be NULL */,
+                                double distance_thresh, double* pose, double* E /* may be NULL */, int* pose_found,
+                                int* n_good, unsigned char* mask_out /* may be NULL */, double* xyz /* may be NULL */);
+
+/* `triangulatePoints(projMatr1, projMatr2, projPoints1, projPoints2, points4D)`:
+ * step 4 above alone, with the caller's cameras (row-major 3x4 doubles) and
+ * points as given -- no normalisation, and xyzw (n x 4 doubles) is the
+ * homogeneous eigenvector, not divided by w, as cv::triangulatePoints divides
+ * nothing.  It is the per-pair function of pose recovery, compiled once.  Host
+ * code, no context; SIFT_E_INVALID for a NULL buffer or n < 0. */
+int sift_triangulate_points(const double* P_src, const double* P_dst, const float* src_xy, const float* dst_xy, int n,
+                            double* xyzw);
+/* The same for every segment, on the device in stream order: segment b's rows
+ * (clamped as above) are solved under d_P_src + 12 b and d_P_dst + 12 b into
+ * d_xyzw [m_cap][4] by pair row; rows outside the segments are never written.
+ * Context stream, no synchronisation, no scratch, no host value read; the
+ * entry-point rules of sift_recover_pose_segmented_device. */
+int sift_triangulate_points_segmented_device(sift_ctx* ctx, const float* d_src_xy, const float* d_dst_xy,
+                                             const int* d_m_offsets, int n_segments, int m_cap, const double* d_P_src,
+                                             const double* d_P_dst, double* d_xyzw);
+
 /* ---- self-test ------------------------------------------------------------ */
 /* Evaluates one device arithmetic helper element-wise on host arrays (n
  * values), for bit-exact checks of the GPU math against the CPU oracle:

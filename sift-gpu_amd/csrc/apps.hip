@@ -489,6 +489,32 @@ int fundamental_device(sift_ctx* c, const float* src_xy, const float* dst_xy, co
   return SIFT_OK;
 }
 
+// ---- a whole batch: recoverPose per segment of the same pairs, and triangulatePoints ----
+int check_pose(sift_ctx* c, const float* src_xy, const float* dst_xy, const int* m_offsets, int n_segments, int m_cap,
+               const double* F, const int* found, const double* K_src, const double* K_dst, int k_per_segment,
+               const double* pose, const int* pose_found, const int* n_good) {
+  if (!c) return SIFT_E_INVALID;
+  if (n_segments < 0 || m_cap < 0) return fail(c, SIFT_E_INVALID, "negative count");
+  if (k_per_segment != 0 && k_per_segment != 1) return fail(c, SIFT_E_INVALID, "k_per_segment must be 0 or 1");
+  if (n_segments == 0 || m_cap == 0) return SIFT_OK;
+  if (!src_xy || !dst_xy || !m_offsets || !F || !found || !K_src || !K_dst || !pose || !pose_found || !n_good)
+    return fail(c, SIFT_E_INVALID, "null buffer");
+  return SIFT_OK;
+}
+
+int pose_device(sift_ctx* c, const float* src_xy, const float* dst_xy, const int* moff, int n_segments, int m_cap,
+                const double* F, const int* found, const double* K_src, const double* K_dst, int k_per_segment,
+                const unsigned char* mask_in, double distance_thresh, double* pose, double* E, int* pose_found,
+                int* n_good, unsigned char* mask_out, double* xyz) {
+  {
+    StageScope sc(c, ST_POSE_SEG);  // the work depends on offsets and points only the device knows
+    launch_recover_pose_seg(c->stream, src_xy, dst_xy, moff, n_segments, m_cap, F, found, K_src, K_dst, k_per_segment,
+                            mask_in, distance_thresh, pose, E, pose_found, n_good, mask_out, xyz);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
 // ---- readImage front end, src/main.cpp:79-87 ----
 int check_bgr(sift_ctx* c, const void* bgr, int batch, int rows, int cols, int out_rows, int out_cols,
               const void* gray) {
@@ -1103,6 +1129,105 @@ int sift_find_fundamental_segmented(sift_ctx* c, const float* src_xy, const floa
   if (inlier_mask && hi > lo)
     HIP_TRY(c, hipMemcpyAsync(inlier_mask + lo, S.mask + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SIFT_OK;
+}
+
+// ---- recoverPose / triangulatePoints: one pair set on the host, a batch on the device ----
+int sift_recover_pose(const double* F, const double* K_src, const double* K_dst, const float* src_xy,
+                      const float* dst_xy, int n, const unsigned char* mask_in, double distance_thresh, double* pose,
+                      double* E, unsigned char* mask_out, double* xyz, int* n_good) {
+  if (!F || !K_src || !K_dst || !pose || !n_good || n < 0 || (n > 0 && (!src_xy || !dst_xy)))
+    return SIFT_E_INVALID;
+  // none: recover_pose has zeroed every output
+  return recover_pose(F, K_src, K_dst, src_xy, dst_xy, n, mask_in, distance_thresh, pose, E, mask_out, xyz, n_good)
+             ? SIFT_OK
+             : SIFT_E_INVALID;
+}
+
+int sift_recover_pose_segmented_device(sift_ctx* c, const float* d_src_xy, const float* d_dst_xy,
+                                       const int* d_m_offsets, int n_segments, int m_cap, const double* d_F,
+                                       const int* d_found, const double* d_K_src, const double* d_K_dst,
+                                       int k_per_segment, const unsigned char* d_mask_in, double distance_thresh,
+                                       double* d_pose, double* d_E, int* d_pose_found, int* d_n_good,
+                                       unsigned char* d_mask_out, double* d_xyz) {
+  int rc = check_pose(c, d_src_xy, d_dst_xy, d_m_offsets, n_segments, m_cap, d_F, d_found, d_K_src, d_K_dst,
+                      k_per_segment, d_pose, d_pose_found, d_n_good);
+  if (rc || n_segments == 0 || m_cap == 0) return rc;
+  (void)hipSetDevice(c->device);
+  return pose_device(c, d_src_xy, d_dst_xy, d_m_offsets, n_segments, m_cap, d_F, d_found, d_K_src, d_K_dst,
+                     k_per_segment, d_mask_in, distance_thresh, d_pose, d_E, d_pose_found, d_n_good, d_mask_out,
+                     d_xyz);
+}
+
+int sift_recover_pose_segmented(sift_ctx* c, const float* src_xy, const float* dst_xy, const int* m_offsets,
+                                int n_segments, int m_cap, const double* F, const int* found, const double* K_src,
+                                const double* K_dst, int k_per_segment, const unsigned char* mask_in,
+                                double distance_thresh, double* pose, double* E, int* pose_found, int* n_good,
+                                unsigned char* mask_out, double* xyz) {
+  int rc = check_pose(c, src_xy, dst_xy, m_offsets, n_segments, m_cap, F, found, K_src, K_dst, k_per_segment, pose,
+                      pose_found, n_good);
+  if (rc || n_segments == 0 || m_cap == 0) return rc;
+  (void)hipSetDevice(c->device);
+  PoseHost S;
+  if ((rc = carve(c, &S, [&](Carver& a) { return pose_host_layout(a, n_segments, m_cap, k_per_segment); }))) return rc;
+  const size_t xyb = (size_t)m_cap * 2 * sizeof(float), ob = (size_t)(n_segments + 1) * sizeof(int);
+  const size_t kb = (k_per_segment ? (size_t)n_segments : 1) * 9 * sizeof(double);
+  const int lo = clamp_off(m_offsets[0], m_cap), hi = clamp_off(m_offsets[n_segments], m_cap);
+  HIP_TRY(c, hipMemcpyAsync(S.in.src_xy, src_xy, xyb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.in.dst_xy, dst_xy, xyb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.in.m_off, m_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.in.H, F, (size_t)n_segments * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.in.found, found, (size_t)n_segments * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.K_src, K_src, kb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.K_dst, K_dst, kb, hipMemcpyHostToDevice, c->stream));
+  if (mask_in) HIP_TRY(c, hipMemcpyAsync(S.in.mask, mask_in, (size_t)m_cap, hipMemcpyHostToDevice, c->stream));
+  // rows of [lo, hi) that no segment owns (offsets that skip rows) go out and come back as they are
+  if (mask_out && hi > lo)
+    HIP_TRY(c, hipMemcpyAsync(S.mask_out + lo, mask_out + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, c->stream));
+  if (xyz && hi > lo)
+    HIP_TRY(c, hipMemcpyAsync(S.xyz + (size_t)lo * 3, xyz + (size_t)lo * 3, (size_t)(hi - lo) * 3 * sizeof(double),
+                              hipMemcpyHostToDevice, c->stream));
+  if ((rc = pose_device(c, S.in.src_xy, S.in.dst_xy, S.in.m_off, n_segments, m_cap, S.in.H, S.in.found, S.K_src,
+                        S.K_dst, k_per_segment, mask_in ? S.in.mask : nullptr, distance_thresh, S.pose,
+                        E ? S.E : nullptr, S.pose_found, S.n_good, mask_out ? S.mask_out : nullptr,
+                        xyz ? S.xyz : nullptr)))
+    return rc;
+  HIP_TRY(c, hipMemcpyAsync(pose, S.pose, (size_t)n_segments * 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (E) HIP_TRY(c, hipMemcpyAsync(E, S.E, (size_t)n_segments * 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(pose_found, S.pose_found, (size_t)n_segments * sizeof(int), hipMemcpyDeviceToHost,
+                            c->stream));
+  HIP_TRY(c, hipMemcpyAsync(n_good, S.n_good, (size_t)n_segments * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  // only the segments' rows come back: the others are left untouched, as in the device form
+  if (mask_out && hi > lo)
+    HIP_TRY(c, hipMemcpyAsync(mask_out + lo, S.mask_out + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, c->stream));
+  if (xyz && hi > lo)
+    HIP_TRY(c, hipMemcpyAsync(xyz + (size_t)lo * 3, S.xyz + (size_t)lo * 3, (size_t)(hi - lo) * 3 * sizeof(double),
+                              hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SIFT_OK;
+}
+
+int sift_triangulate_points(const double* P_src, const double* P_dst, const float* src_xy, const float* dst_xy, int n,
+                            double* xyzw) {
+  if (!P_src || !P_dst || n < 0 || (n > 0 && (!src_xy || !dst_xy || !xyzw))) return SIFT_E_INVALID;
+  triangulate_points(P_src, P_dst, src_xy, dst_xy, n, xyzw);
+  return SIFT_OK;
+}
+
+int sift_triangulate_points_segmented_device(sift_ctx* c, const float* d_src_xy, const float* d_dst_xy,
+                                             const int* d_m_offsets, int n_segments, int m_cap, const double* d_P_src,
+                                             const double* d_P_dst, double* d_xyzw) {
+  if (!c) return SIFT_E_INVALID;
+  if (n_segments < 0 || m_cap < 0) return fail(c, SIFT_E_INVALID, "negative count");
+  if (n_segments == 0 || m_cap == 0) return SIFT_OK;
+  if (!d_src_xy || !d_dst_xy || !d_m_offsets || !d_P_src || !d_P_dst || !d_xyzw)
+    return fail(c, SIFT_E_INVALID, "null buffer");
+  (void)hipSetDevice(c->device);
+  {
+    StageScope sc(c, ST_TRI_SEG);  // the work depends on offsets only the device knows
+    launch_triangulate_seg(c->stream, d_src_xy, d_dst_xy, d_m_offsets, n_segments, m_cap, d_P_src, d_P_dst, d_xyzw);
+  }
+  HIP_TRY(c, hipGetLastError());
   return SIFT_OK;
 }
 

@@ -303,6 +303,21 @@ int find_fundamental_ransac(const float* src_xy, const float* dst_xy, int n, dou
 void launch_fundamental_seg(hipStream_t st, const float* src_xy, const float* dst_xy, const int* moff, int n_segments,
                             int m_cap, double thr, int max_iters, double confidence, double* F, int* found,
                             unsigned char* mask_out);
+// pose.hip: recoverPose (cheirality over four candidate poses of E = K_dst^T F K_src) and triangulatePoints
+// on the host; pose is [R | t] row-major (12), xyz [n][3], xyzw [n][4]; mask_in, E, mask_out, xyz may be null.
+int recover_pose(const double* F, const double* K_src, const double* K_dst, const float* src_xy, const float* dst_xy,
+                 int n, const unsigned char* mask_in, double distance_thresh, double* pose, double* E,
+                 unsigned char* mask_out, double* xyz, int* n_good);
+void triangulate_points(const double* P_src, const double* P_dst, const float* src_xy, const float* dst_xy, int n,
+                        double* xyzw);
+// pose_batch.hip: the same per segment; one workgroup each, no scratch.  K is one 3x3 (k_per_segment 0) or
+// [n_segments][9]; pose is [n_segments][12], E [n_segments][9], xyz [m_cap][3]; P_src / P_dst [n_segments][12].
+void launch_recover_pose_seg(hipStream_t st, const float* src_xy, const float* dst_xy, const int* moff, int n_segments,
+                             int m_cap, const double* F, const int* found, const double* K_src, const double* K_dst,
+                             int k_per_segment, const unsigned char* mask_in, double distance_thresh, double* pose,
+                             double* E, int* pose_found, int* n_good, unsigned char* mask_out, double* xyz);
+void launch_triangulate_seg(hipStream_t st, const float* src_xy, const float* dst_xy, const int* moff, int n_segments,
+                            int m_cap, const double* P_src, const double* P_dst, double* xyzw);
 // sift_selftest_math ops 8 / 9: out[i] = update_num_iters(confidence, (good[i] of n[i] pairs), 4, 2000)
 void launch_update_num_iters_selftest(hipStream_t st, double confidence, const float* good, const float* n, float* out,
                                       int count);

@@ -160,6 +160,56 @@ SIFT_HD void smallest_eigvec(double A[N][N], double* v) {
     }
 }
 
+// smallest_eigvec's sibling for a caller that needs every eigenpair
+// (pose_math.hpp): the same sweeps, statement for statement, then all of V
+// (eigenvectors in columns) and A's diagonal in d, unordered.  A function of
+// its own, so that smallest_eigvec keeps the statements its tests pin.
+template <int N>
+SIFT_HD void sym_eig(double A[N][N], double V[N][N], double* d) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = 0; j < N; ++j) V[i][j] = i == j;
+#pragma unroll 1
+  for (int sweep = 0; sweep < 60; ++sweep) {
+    double off = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+      for (int j = i + 1; j < N; ++j) off += A[i][j] * A[i][j];
+    if (off < 1e-300) break;
+#pragma unroll
+    for (int p = 0; p < N; ++p)
+#pragma unroll
+      for (int q = p + 1; q < N; ++q) {
+        if (fabs(A[p][q]) < 1e-300) continue;
+        const double th = (A[q][q] - A[p][p]) / (2 * A[p][q]);
+        const double t = (th >= 0 ? 1 : -1) / (fabs(th) + sqrt(th * th + 1));
+        const double c = 1 / sqrt(t * t + 1), s = t * c;
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+          const double akp = A[k][p], akq = A[k][q];
+          A[k][p] = c * akp - s * akq;
+          A[k][q] = s * akp + c * akq;
+        }
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+          const double apk = A[p][k], aqk = A[q][k];
+          A[p][k] = c * apk - s * aqk;
+          A[q][k] = s * apk + c * aqk;
+        }
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+          const double vkp = V[k][p], vkq = V[k][q];
+          V[k][p] = c * vkp - s * vkq;
+          V[k][q] = s * vkp + c * vkq;
+        }
+      }
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) d[i] = A[i][i];
+}
+
 SIFT_HD void mat3mul(const double* a, const double* b, double* c) {
 #pragma unroll
   for (int i = 0; i < 3; ++i)

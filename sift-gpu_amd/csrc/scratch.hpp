@@ -397,4 +397,20 @@ constexpr int kFundRound = 256;
 // stages (pairs, offsets, nine doubles and a flag per segment, the mask):
 // affine_host_layout is its layout too.
 
+// ---- relative pose and triangulation (pose_batch.hip) ----
+// sift_recover_pose_segmented_device and sift_triangulate_points_segmented_device
+// carve nothing: a segment's decomposition and its four counts live in LDS.
+// sift_recover_pose_segmented stages the estimate's layout (pairs, offsets, F in
+// H, found, the mask read), then the calibrations and the results.
+struct PoseHost {
+  AffineHost in; double *K_src, *K_dst, *pose, *E; int *pose_found, *n_good; unsigned char* mask_out; double* xyz;
+};
+inline PoseHost pose_host_layout(Carver& a, int n_segments, int m_cap, int k_per_segment) {
+  const size_t ks = k_per_segment ? (size_t)n_segments * 9 : 9;
+  return {affine_host_layout(a, n_segments, m_cap), a.take<double>(ks), a.take<double>(ks),
+          a.take<double>((size_t)n_segments * 12), a.take<double>((size_t)n_segments * 9),
+          a.take<int>((size_t)n_segments), a.take<int>((size_t)n_segments), a.take<unsigned char>((size_t)m_cap),
+          a.take<double>((size_t)m_cap * 3)};
+}
+
 }  // namespace sift

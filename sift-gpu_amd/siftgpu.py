@@ -87,7 +87,7 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} not built (run make -C {HERE}); no CPU fallback exists")
         L = ctypes.CDLL(LIB_PATH)
         vp, ip, fp, sz = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.c_size_t
-        pint = ctypes.POINTER(ctypes.c_int)
+        pint, pdbl = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)
         sigs = {
             "sift_ctx_create": (ip, [ip, ip, ip, ip, ctypes.c_uint, ctypes.POINTER(vp)]),
             "sift_ctx_destroy": (ip, [vp]),
@@ -184,6 +184,13 @@ def lib():
                                                             ctypes.c_double, vp, vp, vp]),
             "sift_find_fundamental_segmented": (ip, [vp, fp, fp, pint, ip, ip, ctypes.c_double, ip, ctypes.c_double,
                                                      ctypes.POINTER(ctypes.c_double), pint, vp]),
+            "sift_recover_pose": (ip, [pdbl, pdbl, pdbl, fp, fp, ip, vp, ctypes.c_double, pdbl, pdbl, vp, vp, pint]),
+            "sift_recover_pose_segmented_device": (ip, [vp, vp, vp, vp, ip, ip, vp, vp, vp, vp, ip, vp,
+                                                        ctypes.c_double, vp, vp, vp, vp, vp, vp]),
+            "sift_recover_pose_segmented": (ip, [vp, fp, fp, pint, ip, ip, pdbl, pint, pdbl, pdbl, ip, vp,
+                                                 ctypes.c_double, pdbl, pdbl, pint, pint, vp, vp]),
+            "sift_triangulate_points": (ip, [pdbl, pdbl, fp, fp, ip, pdbl]),
+            "sift_triangulate_points_segmented_device": (ip, [vp, vp, vp, vp, ip, ip, vp, vp, vp]),
             "sift_multi_shard": (ip, [ip, ip, ip, pint, pint]),
             "sift_multi_merge_offsets": (ip, [ctypes.POINTER(pint), pint, ip, pint]),
             "sift_multi_create": (ip, [pint, ip, ip, ip, ip, ctypes.c_uint, ip, ip, ip, ctypes.POINTER(vp)]),
@@ -213,7 +220,9 @@ def lib():
                     "sift_estimate_affine_segmented_device", "sift_estimate_affine_segmented",
                     "sift_find_fundamental", "sift_find_fundamental_segmented_device",
                     "sift_find_fundamental_segmented", "sift_knn_match_epipolar_segmented_device",
-                    "sift_knn_match_epipolar_segmented"}  # absent from older builds (A/B runs against a saved library)
+                    "sift_knn_match_epipolar_segmented", "sift_recover_pose",
+                    "sift_recover_pose_segmented_device", "sift_recover_pose_segmented", "sift_triangulate_points",
+                    "sift_triangulate_points_segmented_device"}  # absent from older builds (A/B runs against a saved library)
         for name, (res, args) in sigs.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -1133,6 +1142,84 @@ class Context:
         return [(F[b].reshape(3, 3).copy() if found[b] else None, mask[o[b]:max(o[b], o[b + 1])].copy())
                 for b in range(nseg)]
 
+    # ---- a whole batch: relative pose per segment from its fundamental matrix, and triangulation ---
+    def recover_pose_segmented_device(self, src_xy_ptr: int, dst_xy_ptr: int, m_offsets_ptr: int, n_segments: int,
+                                      m_cap: int, F_ptr: int, found_ptr: int, K_src_ptr: int, K_dst_ptr: int,
+                                      pose_ptr: int, pose_found_ptr: int, n_good_ptr: int, k_per_segment: int = 0,
+                                      mask_in_ptr: int | None = None, distanceThresh: float = 50.0,
+                                      E_ptr: int | None = None, mask_out_ptr: int | None = None,
+                                      xyz_ptr: int | None = None):
+        """Device-pointer form (no sync) of recoverPose for every segment
+        [m_offsets[b], m_offsets[b+1]) of the point pairs: F_ptr / found_ptr /
+        mask_in_ptr exactly as find_fundamental_segmented_device leaves them,
+        K_*_ptr one 3x3 float64 each (k_per_segment 0) or [n_segments][9] (1);
+        pose_ptr [n_segments][12] float64 ([R | t] by rows), pose_found_ptr and
+        n_good_ptr [n_segments] int32, E_ptr [n_segments][9], mask_out_ptr [m_cap]
+        uint8 and xyz_ptr [m_cap][3] float64 or None."""
+        vp = lambda p: ctypes.c_void_p(p or None)  # noqa: E731
+        self._check("sift_recover_pose_segmented_device",
+                    self._L.sift_recover_pose_segmented_device(
+                        self.h, vp(src_xy_ptr), vp(dst_xy_ptr), vp(m_offsets_ptr), n_segments, m_cap, vp(F_ptr),
+                        vp(found_ptr), vp(K_src_ptr), vp(K_dst_ptr), int(k_per_segment), vp(mask_in_ptr),
+                        float(distanceThresh), vp(pose_ptr), vp(E_ptr), vp(pose_found_ptr), vp(n_good_ptr),
+                        vp(mask_out_ptr), vp(xyz_ptr)))
+
+    def recoverPoseBatch(self, F, found, K_src, K_dst, src, dst, m_offsets, mask=None, distanceThresh: float = 50.0):
+        """recoverPose for every segment at once (host arrays): F [n_segments, 3, 3]
+        or [n_segments, 9] and found [n_segments] as findFundamentalBatch gives
+        them (None / 0 = no model), K_src / K_dst one 3x3 or [n_segments, 3, 3],
+        mask [n] or None -> a list of (R 3x3, t 3, E 3x3, mask uint8[segment's
+        pairs], xyz float64[segment's pairs, 3], n_good) per segment, R = t = E =
+        None where the segment has no pose; offsets clamped to the number of pairs."""
+        s = np.ascontiguousarray(src, np.float32).reshape(-1, 2)
+        d = np.ascontiguousarray(dst, np.float32).reshape(-1, 2)
+        mo = np.ascontiguousarray(m_offsets, np.int32)
+        if len(s) != len(d) or mo.ndim != 1 or len(mo) < 1:
+            raise ValueError("src / dst must be [n, 2] and m_offsets n_segments + 1 entries")
+        nseg, n = len(mo) - 1, len(s)
+        Fa = np.ascontiguousarray(np.asarray(F, np.float64).reshape(nseg, 9))
+        fa = np.ascontiguousarray(found, np.int32).reshape(nseg)
+        Ks = np.ascontiguousarray(K_src, np.float64).reshape(-1, 9)
+        Kd = np.ascontiguousarray(K_dst, np.float64).reshape(-1, 9)
+        per = 0 if len(Ks) == 1 and len(Kd) == 1 else 1
+        if per and (len(Ks) != nseg or len(Kd) != nseg):
+            raise ValueError("K_src / K_dst must both be one 3x3 or both [n_segments, 3, 3]")
+        mi = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        if mi is not None and len(mi) != n:
+            raise ValueError("mask must have one byte per pair")
+        pose, E = np.zeros((nseg, 12), np.float64), np.zeros((nseg, 9), np.float64)
+        pf, ng = np.zeros(nseg, np.int32), np.zeros(nseg, np.int32)
+        mout, xyz = np.zeros(n, np.uint8), np.zeros((n, 3), np.float64)
+        pint, pdbl = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)
+        self._check("sift_recover_pose_segmented",
+                    self._L.sift_recover_pose_segmented(
+                        self.h, _fp(s), _fp(d), mo.ctypes.data_as(pint), nseg, n, Fa.ctypes.data_as(pdbl),
+                        fa.ctypes.data_as(pint), Ks.ctypes.data_as(pdbl), Kd.ctypes.data_as(pdbl), per,
+                        None if mi is None else mi.ctypes.data, float(distanceThresh), pose.ctypes.data_as(pdbl),
+                        E.ctypes.data_as(pdbl), pf.ctypes.data_as(pint), ng.ctypes.data_as(pint), mout.ctypes.data,
+                        xyz.ctypes.data))
+        o = np.clip(mo.astype(np.int64), 0, n)
+        out = []
+        for b in range(nseg):
+            rows = slice(o[b], max(o[b], o[b + 1]))
+            P = pose[b].reshape(3, 4)
+            out.append((P[:, :3].copy() if pf[b] else None, P[:, 3].copy() if pf[b] else None,
+                        E[b].reshape(3, 3).copy() if pf[b] else None, mout[rows].copy(), xyz[rows].copy(), int(ng[b])))
+        return out
+
+    def triangulate_points_segmented_device(self, src_xy_ptr: int, dst_xy_ptr: int, m_offsets_ptr: int,
+                                            n_segments: int, m_cap: int, P_src_ptr: int, P_dst_ptr: int,
+                                            xyzw_ptr: int):
+        """Device-pointer form (no sync) of triangulatePoints for every segment of
+        the point pairs under its own cameras: P_*_ptr [n_segments][12] float64
+        (recover_pose_segmented_device's pose_ptr is a P_dst), xyzw_ptr [m_cap][4]
+        float64, homogeneous and not divided."""
+        vp = lambda p: ctypes.c_void_p(p or None)  # noqa: E731
+        self._check("sift_triangulate_points_segmented_device",
+                    self._L.sift_triangulate_points_segmented_device(
+                        self.h, vp(src_xy_ptr), vp(dst_xy_ptr), vp(m_offsets_ptr), n_segments, m_cap, vp(P_src_ptr),
+                        vp(P_dst_ptr), vp(xyzw_ptr)))
+
     # ---- device batch API ------------------------------------------------
     def synth_images(self, out_ptr: int, batch: int, rows: int, cols: int, row_stride: int,
                      img_stride: int, seed_base: int = 0):
@@ -1669,6 +1756,52 @@ def findFundamentalMat(src, dst, thr: float = 3.0, max_iters: int = 1000, confid
     if rc != SIFT_OK:
         return None, np.zeros(len(s), np.uint8)
     return F.reshape(3, 3), m[:len(s)]
+
+
+def recoverPose(F, K_src, K_dst, src, dst, mask=None, distanceThresh: float = 50.0):
+    """cv::recoverPose(E, points1, points2, K, R, t, distanceThresh, mask, triangulatedPoints) for
+    E = K_dst^T F K_src -> (R 3x3, t 3, E 3x3, mask uint8[n], xyz float64[n, 3], n_good), with
+    X_dst = R X_src + t and xyz in the src camera's frame; R = t = E = None when there is no pose.
+    Host code in the library (pose.hip; include/sift_hip.h has the rule)."""
+    s = np.ascontiguousarray(src, np.float32).reshape(-1, 2)
+    d = np.ascontiguousarray(dst, np.float32).reshape(-1, 2)
+    if len(s) != len(d):
+        raise ValueError("point counts differ")
+    n = len(s)
+    Fa = np.ascontiguousarray(F, np.float64).reshape(9)
+    Ks, Kd = np.ascontiguousarray(K_src, np.float64).reshape(9), np.ascontiguousarray(K_dst, np.float64).reshape(9)
+    mi = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
+    if mi is not None and len(mi) != n:
+        raise ValueError("mask must have one byte per pair")
+    pose, E = np.zeros(12, np.float64), np.zeros(9, np.float64)
+    mout, xyz = np.zeros(max(n, 1), np.uint8), np.zeros((max(n, 1), 3), np.float64)
+    ng = ctypes.c_int(0)
+    pdbl = ctypes.POINTER(ctypes.c_double)
+    rc = lib().sift_recover_pose(Fa.ctypes.data_as(pdbl), Ks.ctypes.data_as(pdbl), Kd.ctypes.data_as(pdbl), _fp(s),
+                                 _fp(d), n, None if mi is None else mi.ctypes.data, float(distanceThresh),
+                                 pose.ctypes.data_as(pdbl), E.ctypes.data_as(pdbl), mout.ctypes.data, xyz.ctypes.data,
+                                 ctypes.byref(ng))
+    if rc != SIFT_OK:
+        return None, None, None, np.zeros(n, np.uint8), np.zeros((n, 3), np.float64), 0
+    P = pose.reshape(3, 4)
+    return P[:, :3].copy(), P[:, 3].copy(), E.reshape(3, 3), mout[:n], xyz[:n], ng.value
+
+
+def triangulatePoints(P_src, P_dst, src, dst):
+    """cv::triangulatePoints(projMatr1, projMatr2, projPoints1, projPoints2) -> float64 [n, 4],
+    homogeneous and not divided (OpenCV returns the transpose, 4 x n).  Host code in the library."""
+    s = np.ascontiguousarray(src, np.float32).reshape(-1, 2)
+    d = np.ascontiguousarray(dst, np.float32).reshape(-1, 2)
+    if len(s) != len(d):
+        raise ValueError("point counts differ")
+    Ps, Pd = np.ascontiguousarray(P_src, np.float64).reshape(12), np.ascontiguousarray(P_dst, np.float64).reshape(12)
+    out = np.zeros((max(len(s), 1), 4), np.float64)
+    pdbl = ctypes.POINTER(ctypes.c_double)
+    rc = lib().sift_triangulate_points(Ps.ctypes.data_as(pdbl), Pd.ctypes.data_as(pdbl), _fp(s), _fp(d), len(s),
+                                       out.ctypes.data_as(pdbl))
+    if rc != SIFT_OK:
+        raise SiftError("sift_triangulate_points", rc, "bad argument")
+    return out[:len(s)]
 
 
 WARP_INVERSE_MAP = 16  # cv::WARP_INVERSE_MAP

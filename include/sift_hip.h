@@ -1265,6 +1265,100 @@ int sift_triangulate_points_segmented_device(sift_ctx* ctx, const float* d_src_x
                                              const int* d_m_offsets, int n_segments, int m_cap, const double* d_P_src,
                                              const double* d_P_dst, double* d_xyzw);
 
+/* ---- lens undistortion: images and point rows (the calls in front of the chain) ----
+ * dst = cv::undistort(src, K, dist, newK) with INTER_LINEAR and BORDER_CONSTANT 0,
+ * and cv::undistortPoints(src, dst, K, dist, noArray(), P), for OpenCV's
+ * 8-coefficient rational model: dist is always eight doubles
+ * (k1, k2, p1, p2, k3, k4, k5, k6), unused ones zero.  K, newK and P are
+ * row-major 3x3 doubles and may be any invertible matrix (P any finite one).
+ * Stated here as the library's own rule (csrc/undistort_math.hpp, which host and
+ * device both compile with -ffp-contract=off; restated in numpy in
+ * tests/undistort_oracle.py): double + - * /, rint and the float blend, no libm
+ * call.  It is not bit-compatible with OpenCV (whose undistort goes through
+ * float maps and whose undistortPoints stops on a criterion); parity is by
+ * construction and unpinned -- no OpenCV here.
+ * The inverse of a calibration is K^-1 = adj(K) / det(K) exactly as step 1 of
+ * sift_recover_pose forms it (nine cofactors, det = K0 c0 + K1 c3 + K2 c6, each
+ * entry one divide).  A camera has no rule -- an image undistorts to zeros, a
+ * segment's rows are zeros and its flag 0 -- when an entry of K, newK, P or
+ * dist is not finite, or det(K) or det(newK) is zero or not finite or an entry
+ * of the inverse is not finite.
+ * The model's terms at normalised (x, y), in double, every multiply and add on
+ * its own:
+ *     xx = x x,  yy = y y,  r2 = xx + yy,
+ *     num = 1 + ((k3 r2 + k2) r2 + k1) r2,  den = 1 + ((k6 r2 + k5) r2 + k4) r2,
+ *     dx = ((2 p1) x) y + p2 (r2 + 2 xx),   dy = p1 (r2 + 2 yy) + ((2 p2) x) y.
+ * project(A, u, v): X = (A0 u + A1 v) + A2, Y = (A3 u + A4 v) + A5,
+ * W = (A6 u + A7 v) + A8, the point (X / W, Y / W).
+ * Images, per destination pixel (u, v): (x, y) = project(newK^-1, u, v);
+ * s = num / den, xd = x s + dx, yd = y s + dy; Wd = (K6 xd + K7 yd) + K8,
+ *     fX = (32 ((K0 xd + K1 yd) + K2)) / Wd,  fY = (32 ((K3 xd + K4 yd) + K5)) / Wd;
+ * from there the statement of sift_warp_perspective takes over unchanged: a NaN
+ * fX or fY makes the pixel 0, the clamp to the int range, rint (ties to even),
+ * the split into sx, ax, sy, ay, samples outside the image are 0 and never
+ * read, and the f32 / u8 blends.
+ * Points, per row (u, v): (x0, y0) = project(K^-1, u, v), x = x0, y = y0;
+ * iters times (OpenCV's count is 5; 0 .. 100), with the terms taken at (x, y):
+ *     icd = den / num,  x = (x0 - dx) icd,  y = (y0 - dy) icd;
+ * then (x, y) = project(P, x, y) where P is given (NULL is the identity and is
+ * not multiplied by: normalised coordinates, as OpenCV gives them; P = K gives
+ * ideal pixels under the same K, what sift_find_fundamental* and
+ * sift_recover_pose* take); then one rounding of each to float.  A NaN row
+ * gives a NaN row and harms no other. */
+/* Images on the device, enqueued on the context stream: one launch, no scratch,
+ * no host value read, no synchronisation.  d_K, d_dist, d_newK hold one camera
+ * for the whole batch (k_per_segment 0: 9, 8, 9 doubles) or one per image
+ * (k_per_segment 1: [n][9], [n][8], [n][9]); d_newK may be NULL: K.  Pixel types
+ * and strides (bytes, 0 = packed; img_stride == 0 with n > 1 is one source image
+ * for every camera) as sift_warp_perspective_segmented_device takes them;
+ * out_rows x out_cols may differ from the source size.  Only the destination
+ * pixels are written; destination rows that are 16-byte aligned (u8: 4-byte)
+ * are written with 16-byte (dword) stores.  Under one shared camera a workgroup
+ * forms its tile's source positions once and walks a group of images with
+ * them.  Errors as the warp call's: a NULL context or buffer, a dimension < 1,
+ * a pixel / channels pair other than F32 x 1, U8 x 1, U8 x 3, a stride too
+ * small, an f32 stride or pointer not a multiple of 4, k_per_segment outside
+ * {0, 1}: SIFT_E_INVALID; a dimension above 2^30: SIFT_E_SIZE; n == 0: SIFT_OK,
+ * nothing enqueued.  Under SIFT_FLAG_PROFILE the stage is "undistort". */
+int sift_undistort_batch_device(sift_ctx* ctx, int pixel, int channels, const void* d_src, int rows, int cols,
+                                size_t row_stride, size_t img_stride, const double* d_K, const double* d_dist,
+                                const double* d_newK /* may be NULL: K */, int k_per_segment, int n, void* d_dst,
+                                int out_rows, int out_cols, size_t out_row_stride, size_t out_img_stride);
+/* Host buffers (synchronous), one image: only the bytes a strided view owns are
+ * read; dst is out_rows x out_cols pixels, packed.  SIFT_E_INVALID with dst
+ * zeroed if the camera has no rule. */
+int sift_undistort(sift_ctx* ctx, int pixel, int channels, const void* src, int rows, int cols, size_t row_stride,
+                   const double* K, const double* dist, const double* newK /* may be NULL: K */, void* dst,
+                   int out_rows, int out_cols);
+/* Points.  A row is an (x, y) float pair; rows are xy_stride_bytes apart in src
+ * and in dst alike (a multiple of 4, at least 8: 8 is a src_xy / dst_xy array,
+ * sizeof(sift_keypoint) a keypoint array, whose other fields are not touched).
+ * dst may be src.  Host code, no context, one camera: SIFT_E_INVALID for a NULL
+ * buffer, n < 0, iters outside 0 .. 100 or a bad stride (nothing written), and
+ * for a camera with no rule (the n rows zeroed). */
+int sift_undistort_points(const double* K, const double* dist, const double* P /* may be NULL: identity */, int iters,
+                          const void* src, void* dst, size_t xy_stride_bytes, int n);
+/* The same for every segment, on the device in stream order: segment b's rows
+ * [m_offsets[b], m_offsets[b + 1]), clamped to m_cap as in
+ * sift_triangulate_points_segmented_device (segments may overlap or run
+ * backwards; with dst == src, overlapping segments are unspecified), go through
+ * camera b (k_per_segment 1: d_K [n][9], d_dist [n][8], d_P [n][9]) or the one
+ * camera (k_per_segment 0); rows outside the segments are never written.
+ * d_ok [n_segments]: 1, or 0 where the segment's camera has no rule (its rows
+ * are zeros); written for every segment, also when m_cap == 0.  Context stream,
+ * one launch, no synchronisation, no scratch, no host value read.  Rows must be
+ * 4-byte aligned. */
+int sift_undistort_points_segmented_device(sift_ctx* ctx, const void* d_src, void* d_dst, size_t xy_stride_bytes,
+                                           const int* d_m_offsets, int n_segments, int m_cap, const double* d_K,
+                                           const double* d_dist, const double* d_P /* may be NULL */,
+                                           int k_per_segment, int iters, int* d_ok);
+/* Host buffers (synchronous): only the rows between the smallest and the largest
+ * clamped offset travel; rows outside the segments keep their bytes. */
+int sift_undistort_points_segmented(sift_ctx* ctx, const void* src, void* dst, size_t xy_stride_bytes,
+                                    const int* m_offsets, int n_segments, int m_cap, const double* K,
+                                    const double* dist, const double* P /* may be NULL */, int k_per_segment,
+                                    int iters, int* ok);
+
 /* ---- self-test ------------------------------------------------------------ */
 /* Evaluates one device arithmetic helper element-wise on host arrays (n
  * values), for bit-exact checks of the GPU math against the CPU oracle:

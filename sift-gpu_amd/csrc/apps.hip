@@ -17,6 +17,7 @@
 
 #include "ctx.hpp"
 #include "scratch.hpp"
+#include "undistort_math.hpp"
 #include "warp_math.hpp"
 
 using namespace sift;
@@ -538,6 +539,38 @@ int check_warp(sift_ctx* c, int pixel, int channels, const void* src, int rows, 
   if (rows > (1 << 30) || cols > (1 << 30) || out_rows > (1 << 30) || out_cols > (1 << 30))
     return fail(c, SIFT_E_SIZE, "a dimension exceeds 2^30");
   *bpp = pixel == SIFT_PIXEL_F32 ? sizeof(float) : (size_t)channels;
+  return SIFT_OK;
+}
+
+// ---- undistort / undistortPoints of a batch (undistort.hip, undistort_math.hpp) ----
+// The checks the device and the host form of the image call share, in the warp call's order.
+int check_undistort(sift_ctx* c, int pixel, int channels, const void* src, int rows, int cols, const double* K,
+                    const double* dist, int k_per_segment, const void* dst, int out_rows, int out_cols, size_t* bpp) {
+  if (!c) return SIFT_E_INVALID;
+  if (!(pixel == SIFT_PIXEL_F32 && channels == 1) && !(pixel == SIFT_PIXEL_U8 && (channels == 1 || channels == 3)))
+    return fail(c, SIFT_E_INVALID, "pixel / channels must be F32 x 1, U8 x 1 or U8 x 3");
+  if (k_per_segment != 0 && k_per_segment != 1) return fail(c, SIFT_E_INVALID, "k_per_segment must be 0 or 1");
+  if (!src || !K || !dist || !dst) return fail(c, SIFT_E_INVALID, "null buffer");
+  if (rows < 1 || cols < 1 || out_rows < 1 || out_cols < 1) return fail(c, SIFT_E_INVALID, "empty image");
+  if (rows > (1 << 30) || cols > (1 << 30) || out_rows > (1 << 30) || out_cols > (1 << 30))
+    return fail(c, SIFT_E_SIZE, "a dimension exceeds 2^30");
+  *bpp = pixel == SIFT_PIXEL_F32 ? sizeof(float) : (size_t)channels;
+  return SIFT_OK;
+}
+
+// The checks the two segmented forms of the point call share; m_cap == 0 still reports the flags.
+int check_undistort_points(sift_ctx* c, const void* src, const void* dst, size_t stride, const int* m_offsets,
+                           int n_segments, int m_cap, const double* K, const double* dist, int k_per_segment,
+                           int iters, const int* ok) {
+  if (!c) return SIFT_E_INVALID;
+  if (n_segments < 0 || m_cap < 0) return fail(c, SIFT_E_INVALID, "negative count");
+  if (k_per_segment != 0 && k_per_segment != 1) return fail(c, SIFT_E_INVALID, "k_per_segment must be 0 or 1");
+  if (!umath::iters_ok(iters)) return fail(c, SIFT_E_INVALID, "iters must be 0 .. 100");
+  if (!umath::stride_ok(stride)) return fail(c, SIFT_E_INVALID, "xy_stride_bytes must be a multiple of 4, at least 8");
+  if (n_segments == 0) return SIFT_OK;
+  if (!m_offsets || !K || !dist || !ok || (m_cap > 0 && (!src || !dst))) return fail(c, SIFT_E_INVALID, "null buffer");
+  if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) % sizeof(float))
+    return fail(c, SIFT_E_INVALID, "point rows must be 4-byte aligned");
   return SIFT_OK;
 }
 
@@ -1307,6 +1340,143 @@ int sift_warp_perspective(sift_ctx* c, int pixel, int channels, const void* src,
                                                    1, flags, S.dst, out_rows, out_cols, out_row, 0)))
     return rc;
   HIP_TRY(c, hipMemcpyAsync(dst, S.dst, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SIFT_OK;
+}
+
+// ---- undistort of every image of a batch through one camera or its own (undistort.hip) ----
+int sift_undistort_batch_device(sift_ctx* c, int pixel, int channels, const void* d_src, int rows, int cols,
+                                size_t row_stride, size_t img_stride, const double* d_K, const double* d_dist,
+                                const double* d_newK, int k_per_segment, int n, void* d_dst, int out_rows,
+                                int out_cols, size_t out_row_stride, size_t out_img_stride) {
+  if (!c) return SIFT_E_INVALID;
+  if (n < 0) return fail(c, SIFT_E_INVALID, "negative count");
+  if (n == 0) return SIFT_OK;
+  size_t bpp = 0;
+  if (int rc = check_undistort(c, pixel, channels, d_src, rows, cols, d_K, d_dist, k_per_segment, d_dst, out_rows,
+                               out_cols, &bpp))
+    return rc;
+  if (row_stride == 0) row_stride = (size_t)cols * bpp;
+  if (out_row_stride == 0) out_row_stride = (size_t)out_cols * bpp;
+  if (out_img_stride == 0) out_img_stride = out_row_stride * out_rows;
+  if (row_stride < (size_t)cols * bpp || (img_stride != 0 && n > 1 && img_stride < row_stride * rows))
+    return fail(c, SIFT_E_INVALID, "source strides too small");
+  if (out_row_stride < (size_t)out_cols * bpp || (n > 1 && out_img_stride < out_row_stride * out_rows))
+    return fail(c, SIFT_E_INVALID, "output strides too small");
+  if (pixel == SIFT_PIXEL_F32 &&
+      ((row_stride | img_stride | out_row_stride | out_img_stride) % sizeof(float) ||
+       ((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst)) % sizeof(float))))
+    return fail(c, SIFT_E_INVALID, "float buffers and strides must be multiples of 4 bytes");
+  (void)hipSetDevice(c->device);
+  {
+    StageScope s(c, ST_UNDISTORT, 0, 2.0 * bpp * out_rows * (double)out_cols * n);
+    launch_undistort(c->stream, pixel == SIFT_PIXEL_U8, channels, d_src, (long long)row_stride, (long long)img_stride,
+                     rows, cols, d_K, d_dist, d_newK, k_per_segment, n, d_dst, (long long)out_row_stride,
+                     (long long)out_img_stride, out_rows, out_cols);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
+int sift_undistort(sift_ctx* c, int pixel, int channels, const void* src, int rows, int cols, size_t row_stride,
+                   const double* K, const double* dist, const double* newK, void* dst, int out_rows, int out_cols) {
+  size_t bpp = 0;
+  int rc = check_undistort(c, pixel, channels, src, rows, cols, K, dist, 0, dst, out_rows, out_cols, &bpp);
+  if (rc) return rc;
+  if (row_stride == 0) row_stride = (size_t)cols * bpp;
+  if (row_stride < (size_t)cols * bpp || (pixel == SIFT_PIXEL_F32 && row_stride % sizeof(float)))
+    return fail(c, SIFT_E_INVALID, "row stride too small for its row, or a float stride not a multiple of 4 bytes");
+  const size_t out_row = (size_t)out_cols * bpp, out_bytes = out_row * out_rows;
+  umath::ImageCam cam;
+  if (!umath::image_camera(K, dist, newK, cam)) {  // the kernel's own rule: nothing to run
+    memset(dst, 0, out_bytes);
+    return fail(c, SIFT_E_INVALID, "the camera undistorts to nothing (singular or non-finite)");
+  }
+  (void)hipSetDevice(c->device);
+  UndistortHost S;  // the matcher's scratch doubles as staging here
+  if ((rc = carve(c, &S, [&](Carver& a) { return undistort_host_layout(a, rows, row_stride, out_rows, out_row); })))
+    return rc;
+  // a strided view (an ROI) owns no padding after its last row: copy only what the image owns
+  const size_t owned = (size_t)(rows - 1) * row_stride + (size_t)cols * bpp;
+  HIP_TRY(c, hipMemcpyAsync(S.src, src, owned, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.K, K, 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.dist, dist, 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (newK) HIP_TRY(c, hipMemcpyAsync(S.newK, newK, 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if ((rc = sift_undistort_batch_device(c, pixel, channels, S.src, rows, cols, row_stride, 0, S.K, S.dist,
+                                        newK ? S.newK : nullptr, 0, 1, S.dst, out_rows, out_cols, out_row, 0)))
+    return rc;
+  HIP_TRY(c, hipMemcpyAsync(dst, S.dst, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SIFT_OK;
+}
+
+// ---- undistortPoints: one camera on the host, every segment of a batch on the device ----
+int sift_undistort_points(const double* K, const double* dist, const double* P, int iters, const void* src, void* dst,
+                          size_t xy_stride_bytes, int n) {
+  if (!K || !dist || n < 0 || (n > 0 && (!src || !dst)) || !umath::iters_ok(iters) ||
+      !umath::stride_ok(xy_stride_bytes))
+    return SIFT_E_INVALID;
+  // a camera with no rule: undistort_points has zeroed the rows
+  return undistort_points(K, dist, P, iters, src, dst, xy_stride_bytes, n) ? SIFT_OK : SIFT_E_INVALID;
+}
+
+int sift_undistort_points_segmented_device(sift_ctx* c, const void* d_src, void* d_dst, size_t xy_stride_bytes,
+                                           const int* d_m_offsets, int n_segments, int m_cap, const double* d_K,
+                                           const double* d_dist, const double* d_P, int k_per_segment, int iters,
+                                           int* d_ok) {
+  int rc = check_undistort_points(c, d_src, d_dst, xy_stride_bytes, d_m_offsets, n_segments, m_cap, d_K, d_dist,
+                                  k_per_segment, iters, d_ok);
+  if (rc || n_segments == 0) return rc;
+  (void)hipSetDevice(c->device);
+  {
+    StageScope sc(c, ST_UNDISTORT);  // the work depends on offsets only the device knows
+    launch_undistort_points_seg(c->stream, d_src, d_dst, (long long)xy_stride_bytes, d_m_offsets, n_segments, m_cap,
+                                d_K, d_dist, d_P, k_per_segment, iters, d_ok);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
+int sift_undistort_points_segmented(sift_ctx* c, const void* src, void* dst, size_t xy_stride_bytes,
+                                    const int* m_offsets, int n_segments, int m_cap, const double* K,
+                                    const double* dist, const double* P, int k_per_segment, int iters, int* ok) {
+  int rc = check_undistort_points(c, src, dst, xy_stride_bytes, m_offsets, n_segments, m_cap, K, dist, k_per_segment,
+                                  iters, ok);
+  if (rc || n_segments == 0) return rc;
+  (void)hipSetDevice(c->device);
+  UndistortPtsHost S;
+  if ((rc = carve(c, &S, [&](Carver& a) {
+         return undistort_pts_host_layout(a, n_segments, m_cap, xy_stride_bytes, k_per_segment);
+       })))
+    return rc;
+  // the rows any segment can own: segments may run backwards, so every offset bounds them
+  int lo = m_cap, hi = 0;
+  for (int b = 0; b <= n_segments; ++b) {
+    const int o = clamp_off(m_offsets[b], m_cap);
+    lo = o < lo ? o : lo;
+    hi = o > hi ? o : hi;
+  }
+  const size_t cams = k_per_segment ? (size_t)n_segments : 1;
+  const size_t at = (size_t)lo * xy_stride_bytes, nb = hi > lo ? (size_t)(hi - lo) * xy_stride_bytes : 0;
+  const bool in_place = src == dst;
+  char* d_dst = reinterpret_cast<char*>(S.dst);
+  char* d_src = in_place ? d_dst : reinterpret_cast<char*>(S.src);
+  if (nb) {
+    // the bytes of a row that are not its (x, y) go out and come back as they are
+    HIP_TRY(c, hipMemcpyAsync(d_dst + at, static_cast<const char*>(dst) + at, nb, hipMemcpyHostToDevice, c->stream));
+    if (!in_place)
+      HIP_TRY(c, hipMemcpyAsync(d_src + at, static_cast<const char*>(src) + at, nb, hipMemcpyHostToDevice, c->stream));
+  }
+  HIP_TRY(c, hipMemcpyAsync(S.m_off, m_offsets, (size_t)(n_segments + 1) * sizeof(int), hipMemcpyHostToDevice,
+                            c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.K, K, cams * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.dist, dist, cams * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (P) HIP_TRY(c, hipMemcpyAsync(S.P, P, cams * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if ((rc = sift_undistort_points_segmented_device(c, d_src, d_dst, xy_stride_bytes, S.m_off, n_segments, m_cap, S.K,
+                                                   S.dist, P ? S.P : nullptr, k_per_segment, iters, S.ok)))
+    return rc;
+  if (nb) HIP_TRY(c, hipMemcpyAsync(static_cast<char*>(dst) + at, d_dst + at, nb, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(ok, S.ok, (size_t)n_segments * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return SIFT_OK;
 }

@@ -276,6 +276,21 @@ void launch_upsample2x(hipStream_t st, const float* src, long long spitch, long 
 void launch_warp_perspective(hipStream_t st, bool u8, int channels, const void* src, long long spitch, long long simg,
                              int rows, int cols, const double* H, const int* found, int n_segments, bool inverse,
                              void* dst, long long dpitch, long long dimg, int orows, int ocols);
+// undistort.hip: cv::undistort of every image of a batch and cv::undistortPoints of every segment of point rows
+// (undistort_math.hpp's rule); strides in bytes, simg 0 = one source for every camera.  K [9], dist [8], newK /
+// P [9] (may be null) are one camera (k_per_segment 0) or one per image / segment.  The image call writes the
+// orows x ocols destination pixels of each image and nothing else; the point call the (x, y) floats of the
+// segments' rows, stride bytes apart (dst may be src), and ok [n_segments].  undistort_points is the host loop
+// for one camera (0: zeros); undistort_group the images a workgroup walks under a shared camera.
+void launch_undistort(hipStream_t st, bool u8, int channels, const void* src, long long spitch, long long simg,
+                      int rows, int cols, const double* K, const double* dist, const double* newK, int k_per_segment,
+                      int n, void* dst, long long dpitch, long long dimg, int orows, int ocols);
+void launch_undistort_points_seg(hipStream_t st, const void* src, void* dst, long long stride, const int* moff,
+                                 int n_segments, int m_cap, const double* K, const double* dist, const double* P,
+                                 int k_per_segment, int iters, int* ok);
+int undistort_points(const double* K, const double* dist, const double* P, int iters, const void* src, void* dst,
+                     size_t stride, int n);
+int undistort_group();
 int find_homography_ransac(const float* src_xy, const float* dst_xy, int n, double thr, int max_iters,
                            double confidence, double* H, unsigned char* mask_out);
 void perspective_transform(const double* H, const float* xy, int n, float* out);

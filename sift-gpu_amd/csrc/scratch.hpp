@@ -413,4 +413,22 @@ inline PoseHost pose_host_layout(Carver& a, int n_segments, int m_cap, int k_per
           a.take<double>((size_t)m_cap * 3)};
 }
 
+// ---- lens undistortion (undistort.hip) ----
+// The device forms carve nothing.  sift_undistort stages one image, its camera
+// (K, the eight coefficients, newK) and the result; sift_undistort_points_segmented
+// the rows read and written (xy_stride bytes each), the offsets, the cameras and the flags.
+struct UndistortHost { uint8_t* src; double *K, *dist, *newK; uint8_t* dst; };
+inline UndistortHost undistort_host_layout(Carver& a, int rows, size_t row_stride, int out_rows, size_t out_row_bytes) {
+  return {a.take<uint8_t>((size_t)rows * row_stride), a.take<double>(9), a.take<double>(8), a.take<double>(9),
+          a.take<uint8_t>((size_t)out_rows * out_row_bytes)};
+}
+struct UndistortPtsHost { float *src, *dst; int* m_off; double *K, *dist, *P; int* ok; };
+inline UndistortPtsHost undistort_pts_host_layout(Carver& a, int n_segments, int m_cap, size_t stride,
+                                                  int k_per_segment) {
+  const size_t cams = k_per_segment ? (size_t)n_segments : 1, row_floats = stride / sizeof(float);
+  return {a.take<float>((size_t)m_cap * row_floats), a.take<float>((size_t)m_cap * row_floats),
+          a.take<int>((size_t)n_segments + 1), a.take<double>(cams * 9), a.take<double>(cams * 8),
+          a.take<double>(cams * 9), a.take<int>((size_t)n_segments)};
+}
+
 }  // namespace sift

@@ -88,12 +88,8 @@ struct Coord {
 SIFT_WARP_HD double clamp_int(double v) {
   return v < -2147483648.0 ? -2147483648.0 : (v > 2147483647.0 ? 2147483647.0 : v);
 }
-SIFT_WARP_HD Coord source_coord(const double* M, const RowTerms& R, int x) {
-  const double xd = (double)x;
-  const double Wd = (M[6] * xd + R.m7y) + M[8];
-  const double W = Wd != 0.0 ? 32.0 / Wd : 0.0;
-  const double fX = ((M[0] * xd + R.m1y) + M[2]) * W;
-  const double fY = ((M[3] * xd + R.m4y) + M[5]) * W;
+// (fX, fY) in 1/32 pixel units to a Coord: the half sift_undistort* shares (undistort_math.hpp).
+SIFT_WARP_HD Coord split_coord(double fX, double fY) {
   Coord c{0, 0, 0, 0, !(fX != fX || fY != fY)};
   if (c.valid) {
     const int X = (int)rint(clamp_int(fX)), Y = (int)rint(clamp_int(fY));  // ties to even
@@ -103,6 +99,14 @@ SIFT_WARP_HD Coord source_coord(const double* M, const RowTerms& R, int x) {
     c.ay = Y & 31;
   }
   return c;
+}
+SIFT_WARP_HD Coord source_coord(const double* M, const RowTerms& R, int x) {
+  const double xd = (double)x;
+  const double Wd = (M[6] * xd + R.m7y) + M[8];
+  const double W = Wd != 0.0 ? 32.0 / Wd : 0.0;
+  const double fX = ((M[0] * xd + R.m1y) + M[2]) * W;
+  const double fY = ((M[3] * xd + R.m4y) + M[5]) * W;
+  return split_coord(fX, fY);
 }
 
 // A sample outside [0, rows) x [0, cols) is the value 0 and is never read.

@@ -191,6 +191,11 @@ def lib():
                                                  ctypes.c_double, pdbl, pdbl, pint, pint, vp, vp]),
             "sift_triangulate_points": (ip, [pdbl, pdbl, fp, fp, ip, pdbl]),
             "sift_triangulate_points_segmented_device": (ip, [vp, vp, vp, vp, ip, ip, vp, vp, vp]),
+            "sift_undistort_batch_device": (ip, [vp, ip, ip, vp, ip, ip, sz, sz, vp, vp, vp, ip, ip, vp, ip, ip, sz, sz]),
+            "sift_undistort": (ip, [vp, ip, ip, vp, ip, ip, sz, pdbl, pdbl, pdbl, vp, ip, ip]),
+            "sift_undistort_points": (ip, [pdbl, pdbl, pdbl, ip, vp, vp, sz, ip]),
+            "sift_undistort_points_segmented_device": (ip, [vp, vp, vp, sz, vp, ip, ip, vp, vp, vp, ip, ip, vp]),
+            "sift_undistort_points_segmented": (ip, [vp, vp, vp, sz, pint, ip, ip, pdbl, pdbl, pdbl, ip, ip, pint]),
             "sift_multi_shard": (ip, [ip, ip, ip, pint, pint]),
             "sift_multi_merge_offsets": (ip, [ctypes.POINTER(pint), pint, ip, pint]),
             "sift_multi_create": (ip, [pint, ip, ip, ip, ip, ctypes.c_uint, ip, ip, ip, ctypes.POINTER(vp)]),
@@ -222,7 +227,9 @@ def lib():
                     "sift_find_fundamental_segmented", "sift_knn_match_epipolar_segmented_device",
                     "sift_knn_match_epipolar_segmented", "sift_recover_pose",
                     "sift_recover_pose_segmented_device", "sift_recover_pose_segmented", "sift_triangulate_points",
-                    "sift_triangulate_points_segmented_device"}  # absent from older builds (A/B runs against a saved library)
+                    "sift_triangulate_points_segmented_device", "sift_undistort_batch_device", "sift_undistort",
+                    "sift_undistort_points", "sift_undistort_points_segmented_device",
+                    "sift_undistort_points_segmented"}  # absent from older builds (A/B runs against a saved library)
         for name, (res, args) in sigs.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -236,6 +243,26 @@ def lib():
 def _fp(a: np.ndarray):
     assert a.dtype == np.float32 and a.flags.c_contiguous
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
+def _pixel_args(img: np.ndarray):
+    """(SIFT_PIXEL_*, channels) of a float32 H x W or uint8 H x W / H x W x 3 image."""
+    if img.dtype == np.float32 and img.ndim == 2:
+        return SIFT_PIXEL_F32, 1
+    if img.dtype == np.uint8 and (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
+        return SIFT_PIXEL_U8, 1 if img.ndim == 2 else 3
+    raise ValueError("expected a float32 H x W or a uint8 H x W / H x W x 3 image")
+
+
+def _camera(K, dist, M):
+    """(K [9], dist [8] zero-padded, M [9] or None) as contiguous float64."""
+    Kd = np.ascontiguousarray(K, np.float64).reshape(9)
+    d = np.asarray(dist, np.float64).reshape(-1)
+    if len(d) > 8:
+        raise ValueError("at most eight distortion coefficients (k1 k2 p1 p2 k3 k4 k5 k6)")
+    dd = np.zeros(8, np.float64)
+    dd[:len(d)] = d
+    return Kd, dd, None if M is None else np.ascontiguousarray(M, np.float64).reshape(9)
 
 
 def _detection_mask(mask, shape):
@@ -540,6 +567,88 @@ class Context:
                         self.h, pixel, channels, vp(src_ptr), rows, cols, row_stride, img_stride, vp(H_ptr),
                         vp(found_ptr or None), n_segments, flags, vp(dst_ptr), out_rows, out_cols, out_row_stride,
                         out_img_stride))
+
+    # ---- lens undistortion (undistort.hip; include/sift_hip.h has the rule) ----
+    def undistort(self, img: np.ndarray, K, dist, newK=None, dsize=None) -> np.ndarray:
+        """cv::undistort(img, K, dist, newK) with INTER_LINEAR and a zero border.  img: float32
+        H x W, or uint8 H x W / H x W x 3; dist: up to eight coefficients (k1 k2 p1 p2 k3 k4 k5 k6);
+        dsize = (width, height) of the result, the source size by default.  A camera with no rule
+        (singular, non-finite) raises SiftError with SIFT_E_INVALID."""
+        img = np.asarray(img)
+        pixel, ch = _pixel_args(img)
+        img = np.ascontiguousarray(img)
+        Kd, dd, Nd = _camera(K, dist, newK)
+        r, c = img.shape[:2]
+        oc, orows = (c, r) if dsize is None else (int(dsize[0]), int(dsize[1]))
+        if oc < 1 or orows < 1:
+            raise ValueError("dsize must be (width, height), both at least 1")
+        out = np.empty((orows, oc) if img.ndim == 2 else (orows, oc, 3), img.dtype)
+        pdbl = ctypes.POINTER(ctypes.c_double)
+        self._check("sift_undistort",
+                    self._L.sift_undistort(self.h, pixel, ch, img.ctypes.data, r, c, 0, Kd.ctypes.data_as(pdbl),
+                                           dd.ctypes.data_as(pdbl), None if Nd is None else Nd.ctypes.data_as(pdbl),
+                                           out.ctypes.data, orows, oc))
+        return out
+
+    def undistort_batch_device(self, pixel: int, channels: int, src_ptr: int, rows: int, cols: int, row_stride: int,
+                               img_stride: int, K_ptr: int, dist_ptr: int, newK_ptr: int, k_per_segment: int, n: int,
+                               dst_ptr: int, out_rows: int, out_cols: int, out_row_stride: int = 0,
+                               out_img_stride: int = 0):
+        """Device-pointer form (no sync): n images through one camera (k_per_segment 0: K_ptr 9,
+        dist_ptr 8, newK_ptr 9 float64, newK_ptr 0 = K) or one per image (k_per_segment 1).
+        Strides in bytes, 0 = packed; img_stride 0 = one source image for every camera."""
+        vp = ctypes.c_void_p
+        self._check("sift_undistort_batch_device",
+                    self._L.sift_undistort_batch_device(
+                        self.h, pixel, channels, vp(src_ptr), rows, cols, row_stride, img_stride, vp(K_ptr),
+                        vp(dist_ptr), vp(newK_ptr or None), int(k_per_segment), n, vp(dst_ptr), out_rows, out_cols,
+                        out_row_stride, out_img_stride))
+
+    def undistort_points_segmented_device(self, src_ptr: int, dst_ptr: int, xy_stride_bytes: int, m_offsets_ptr: int,
+                                          n_segments: int, m_cap: int, K_ptr: int, dist_ptr: int, P_ptr: int,
+                                          k_per_segment: int, iters: int, ok_ptr: int):
+        """Device-pointer form (no sync) of undistortPoints for every segment of (x, y) float rows
+        xy_stride_bytes apart (8: a point array; 28: a keypoint array); dst_ptr may be src_ptr;
+        P_ptr 0 = normalised coordinates; ok_ptr [n_segments] int32."""
+        vp = lambda p: ctypes.c_void_p(p or None)  # noqa: E731
+        self._check("sift_undistort_points_segmented_device",
+                    self._L.sift_undistort_points_segmented_device(
+                        self.h, vp(src_ptr), vp(dst_ptr), xy_stride_bytes, vp(m_offsets_ptr), n_segments, m_cap,
+                        vp(K_ptr), vp(dist_ptr), vp(P_ptr), int(k_per_segment), int(iters), vp(ok_ptr)))
+
+    def undistortPointsSegmented(self, xy, m_offsets, K, dist, P=None, iters: int = 5):
+        """undistortPoints for every segment at once (host arrays): xy float32 [n, 2] or a
+        KEYPOINT_DTYPE array (only x and y change), K / dist / P one camera or one per segment
+        ([n_segments, 3, 3], [n_segments, <= 8], [n_segments, 3, 3]) -> (a new array like xy, ok
+        int32 [n_segments]); rows outside the segments come back as they went in."""
+        a = np.asarray(xy)
+        if a.dtype == KEYPOINT_DTYPE:
+            out, stride = np.ascontiguousarray(a).copy(), KEYPOINT_DTYPE.itemsize
+        else:
+            out, stride = np.ascontiguousarray(a, np.float32).reshape(-1, 2).copy(), 8
+        mo = np.ascontiguousarray(m_offsets, np.int32)
+        if mo.ndim != 1 or len(mo) < 1:
+            raise ValueError("m_offsets must have n_segments + 1 entries")
+        nseg = len(mo) - 1
+        Ka = np.ascontiguousarray(K, np.float64).reshape(-1, 9)
+        per = 0 if len(Ka) == 1 else 1
+        da = np.asarray(dist, np.float64)
+        da = da.reshape(len(Ka), -1) if per else da.reshape(1, -1)
+        if da.shape[1] > 8:
+            raise ValueError("at most eight distortion coefficients (k1 k2 p1 p2 k3 k4 k5 k6)")
+        dd = np.zeros((len(Ka), 8), np.float64)
+        dd[:, :da.shape[1]] = da
+        Pa = None if P is None else np.ascontiguousarray(P, np.float64).reshape(-1, 9)
+        if (per and len(Ka) != nseg) or (Pa is not None and len(Pa) != len(Ka)):
+            raise ValueError("K, dist and P must all be one camera or all one per segment")
+        ok = np.zeros(nseg, np.int32)
+        pint, pdbl = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)
+        self._check("sift_undistort_points_segmented",
+                    self._L.sift_undistort_points_segmented(
+                        self.h, out.ctypes.data, out.ctypes.data, stride, mo.ctypes.data_as(pint), nseg, len(out),
+                        Ka.ctypes.data_as(pdbl), dd.ctypes.data_as(pdbl),
+                        None if Pa is None else Pa.ctypes.data_as(pdbl), per, int(iters), ok.ctypes.data_as(pint)))
+        return out, ok
 
     def calDescriptor(self, gpyr, keypoints: np.ndarray, firstOctave: int = 0) -> np.ndarray:
         r, c = gpyr[0].shape
@@ -1814,3 +1923,33 @@ def warpPerspective(src, M, dsize, flags: int = 0):
     if flags & ~(WARP_INVERSE_MAP | 1):
         raise ValueError("only INTER_LINEAR, optionally with WARP_INVERSE_MAP, is implemented")
     return _ctx(1, 1).warpPerspective(src, M, dsize, inverse=bool(flags & WARP_INVERSE_MAP))
+
+
+def undistort(image, K, dist, newK=None):
+    """cv::undistort(image, K, dist, newK) with INTER_LINEAR and a zero border, for the rational
+    model's (k1 k2 p1 p2 k3 k4 k5 k6).  image: float32 H x W, or uint8 H x W / H x W x 3.  On the
+    GPU (undistort.hip) by the rule in include/sift_hip.h."""
+    return _ctx(1, 1).undistort(image, K, dist, newK)
+
+
+def undistortPoints(xy, K, dist, P=None, iters: int = 5):
+    """cv::undistortPoints(xy, K, dist, noArray(), P) with a fixed iteration count -> float32 [n, 2]:
+    normalised coordinates with P None, ideal pixels with P = K.  xy may be a KEYPOINT_DTYPE array:
+    a copy comes back with only x and y changed.  Host code in the library (undistort.hip;
+    include/sift_hip.h has the rule).  A camera with no rule raises SiftError."""
+    a = np.asarray(xy)
+    if a.dtype == KEYPOINT_DTYPE:
+        out, stride = np.ascontiguousarray(a).copy(), KEYPOINT_DTYPE.itemsize
+    else:
+        out, stride = np.ascontiguousarray(a, np.float32).reshape(-1, 2).copy(), 8
+    if not 0 <= int(iters) <= 100:
+        raise ValueError("iters must be 0 .. 100")
+    Kd, dd, Pd = _camera(K, dist, P)
+    pdbl = ctypes.POINTER(ctypes.c_double)
+    rc = lib().sift_undistort_points(Kd.ctypes.data_as(pdbl), dd.ctypes.data_as(pdbl),
+                                     None if Pd is None else Pd.ctypes.data_as(pdbl), int(iters),
+                                     out.ctypes.data if len(out) else None, out.ctypes.data if len(out) else None,
+                                     stride, len(out))
+    if rc != SIFT_OK:
+        raise SiftError("sift_undistort_points", rc, "the camera has no rule (singular or non-finite)")
+    return out

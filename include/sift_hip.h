@@ -1265,6 +1265,111 @@ int sift_triangulate_points_segmented_device(sift_ctx* ctx, const float* d_src_x
                                              const int* d_m_offsets, int n_segments, int m_cap, const double* d_P_src,
                                              const double* d_P_dst, double* d_xyzw);
 
+/* ---- absolute pose of a view against 3-D points (pnp.hip, pnp_batch.hip) ----- */
+/* `solveP3P` and `solvePnPRansac` for a calibrated view: where is the next frame
+ * relative to the points that sift_recover_pose* left?  Convention: X_cam = R X
+ * + t; a pose is the twelve doubles of [R | t] row by row, what
+ * sift_recover_pose* writes and sift_triangulate_points* takes as P_dst.  xyz is
+ * n x 3 doubles by row, xy the view's n interleaved (x, y) float pixels, row i
+ * belonging to 3-D row i; K a row-major 3x3 double matrix, any invertible one.
+ * The rule (csrc/pnp_math.hpp), in double + - * / and sqrt only, every loop of a
+ * fixed length, no libm outside RANSAC's iteration count:
+ * 1. Calibration.  K^-1 = adj(K) / det(K) as in sift_recover_pose; a singular or
+ *    non-finite K: no model.  A pixel's normalised point (u, v) is K^-1 (x, y,
+ *    1)^T divided by its third component, its bearing (u, v, 1) / sqrt(u u + v v +
+ *    1).
+ * 2. P3P on three rows, the Lambda-Twist route (Persson & Nordberg 2018), which
+ *    needs neither cbrt nor acos.  With a_ij = |x_i - x_j|^2, b_ij = y_i . y_j the
+ *    depths L satisfy L^T M_ij L = a_ij.  D1 = a23 M12 - a12 M23, D2 = a23 M13 -
+ *    a13 M23.  The cubic det(D1 + g D2) has the coefficients det D1, tr(adj(D1)
+ *    D2), tr(adj(D2) D1), det D2; a leading coefficient of exactly zero (or NaN):
+ *    no solution.  Divided by it, the cubic is bisected for 64 steps on [-B, B],
+ *    B = 1 + max |coefficient| (a negative value moves the lower end), then takes
+ *    2 Newton steps (one is skipped where the derivative is zero).  The
+ *    eigenpairs of D0 = D1 + g D2 by the homography's cyclic Jacobi at 3x3; the
+ *    first eigenvalue of smallest magnitude is the zero one, the other two must
+ *    be s1 > 0 > s2, else no solution; s = sqrt(-s2 / s1).  For the line w = e1 +
+ *    s e2, then w = e1 - s e2: l1 = p l2 + q l3 with p = -w1 / w0, q = -w2 / w0;
+ *    L = (p + q tau, 1, tau) in L^T D1 L = 0 is a quadratic a tau^2 + b tau + c;
+ *    none for a negative discriminant; roots (sqrt(disc) - b) / 2a, then
+ *    (-sqrt(disc) - b) / 2a; a root is kept iff tau > 0, p + q tau > 0 and den = 1
+ *    + tau^2 - 2 b23 tau > 0; l2 = sqrt(a23 / den), l3 = tau l2, l1 = (p + q tau)
+ *    l2; five Gauss-Newton steps on the three constraints (3x3 solve by adjugate
+ *    and determinant; a zero determinant ends them).  R = Y X^-1, X's columns x1
+ *    - x2, x1 - x3 and their cross product, Y's the same of l_i y_i, the inverse
+ *    by adjugate and determinant; t = l1 y1 - R x1.  A non-finite entry drops the
+ *    solution.  At most four, in the order (line +, line -) x (root +, root -).
+ *    sift_solve_p3p returns exactly this list: *n_solutions poses at the front of
+ *    poses, the rest zeros.  SIFT_OK also for none (a singular K among them);
+ *    SIFT_E_INVALID for a NULL argument.
+ * 3. A hypothesis is 4 rows: P3P on the first three; of its solutions that put
+ *    the fourth point at z > 0 the first with the smallest squared reprojection
+ *    error of the fourth row in normalised coordinates (an error that is not
+ *    below +inf is no candidate); none: no model.
+ * 4. Inlier test, no division, in double: p = K (R x + t), ex = p0 - x_pix p2, ey =
+ *    p1 - y_pix p2; a row is an inlier iff p2 > 0 && ex ex + ey ey <= (thr thr)(p2
+ *    p2).  A NaN is never an inlier, nor a row whose row_mask byte is 0 (row_mask
+ *    NULL: every row counts).  thr = -8 behaves as 8, thr = 0 admits only an exact
+ *    zero error, thr = +inf every row in front of the camera.  The all-zero rows
+ *    sift_recover_pose* writes for rejected pairs carry a zero byte in its
+ *    mask_out, so with that mask as row_mask they act as outliers: no compaction.
+ * 5. The loop is sift_find_fundamental's with m = 4: n < 4 none; n == 4 a direct
+ *    fit from rows 0..3 with a mask of ones (none if the solve fails or a row is
+ *    masked out); else Rng{~0}, subsets of 4 distinct rows; a subset holding a
+ *    masked-out row, or one whose solve gives nothing, is a counted iteration
+ *    with no model; a hypothesis wins iff good > max(max_good, 3); after a win
+ *    niters = update_num_iters(confidence, (n - good) / n, 4, niters), n the row
+ *    count.  max_iters < 1 or confidence outside (0, 1): none.
+ * 6. Final model.  The mask is the best hypothesis's, taken before the refit.
+ *    The refit minimises the reprojection error in normalised coordinates over
+ *    those inliers: five Gauss-Newton steps on six parameters, R <- R C(d) with
+ *    the Cayley transform C = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a), a = d /
+ *    2, t <- t + dt; Jacobian rows d(X/Z, Y/Z)/dp_c . [-R [x]x | I]; the 21 + 6
+ *    normal-equation sums and the cost in row order; the 6x6 solve by Gaussian
+ *    elimination with partial pivoting (a pivot below 1e-300 ends the loop); a
+ *    step is kept iff the cost fell, else the loop ends; a non-finite result
+ *    leaves the RANSAC model.  R is written as computed.
+ * pose gets [R | t]; inlier_mask (n bytes, may be NULL) the mask; *n_inliers its
+ * count.  SIFT_E_INVALID with every output zeroed when there is no model, and
+ * for a NULL K, pose or n_inliers, NULL rows with n > 0, and n < 0.  Host code, no
+ * context.  The library's own rule, pinned bit for bit against
+ * tests/pnp_oracle.py; not bit-compatible with OpenCV. */
+int sift_solve_p3p(const double* xyz /* [3][3] */, const float* xy /* [3][2] */, const double* K,
+                   double* poses /* [4][12] */, int* n_solutions);
+int sift_solve_pnp(const double* xyz /* [n][3] */, const float* xy /* [n][2] */, int n,
+                   const unsigned char* row_mask /* may be NULL */, const double* K, double reproj_thresh,
+                   int max_iters, double confidence, double* pose /* [12], rows of [R | t] */,
+                   unsigned char* inlier_mask /* [n], may be NULL */, int* n_inliers);
+
+/* The same for every segment of a batch, on the device in stream order, with
+ * the contract of sift_find_fundamental_segmented_device: segment b's rows are
+ * rows [clamp(m_offsets[b]), clamp(m_offsets[b+1])) of d_xyz / d_xy / d_row_mask,
+ * clamped to m_cap (a backwards pair is an empty segment; segments may overlap),
+ * and each segment gets exactly what sift_solve_pnp gives for its rows, bit for
+ * bit.  d_xyz is [m_cap][3] doubles exactly as sift_recover_pose_segmented_device
+ * leaves d_xyz, d_row_mask [m_cap] bytes (may be NULL) exactly as it leaves
+ * d_mask_out; both are only read.  k_per_segment 0: d_K is one 3x3 for all
+ * segments; 1: [n_segments][9].  d_pose is [n_segments][12], d_found and
+ * d_n_inliers [n_segments] ints, d_inlier_mask [m_cap] bytes by row (may be
+ * NULL).  A segment with no model gets a pose of zeros, found 0, n_inliers 0 and
+ * zero mask bytes.  Bytes outside the segments and rows of the per-segment
+ * outputs past n_segments are never written.
+ * Enqueued on the context stream, no synchronisation, no scratch, no host value
+ * read.  A NULL context: SIFT_E_INVALID.  n_segments == 0 or m_cap == 0:
+ * SIFT_OK, nothing enqueued.  A NULL required buffer, a negative count or
+ * k_per_segment outside {0, 1}: SIFT_E_INVALID (sift_last_error names it).
+ * max_iters < 1 or confidence outside (0, 1): every segment found = 0. */
+int sift_solve_pnp_segmented_device(sift_ctx* ctx, const double* d_xyz, const float* d_xy, const int* d_m_offsets,
+                                    int n_segments, int m_cap, const unsigned char* d_row_mask /* may be NULL */,
+                                    const double* d_K, int k_per_segment, double reproj_thresh, int max_iters,
+                                    double confidence, double* d_pose /* [n_segments][12] */, int* d_found,
+                                    int* d_n_inliers, unsigned char* d_inlier_mask /* [m_cap], may be NULL */);
+/* Host buffers (synchronous); xyz / xy / row_mask / inlier_mask have m_cap rows: */
+int sift_solve_pnp_segmented(sift_ctx* ctx, const double* xyz, const float* xy, const int* m_offsets, int n_segments,
+                             int m_cap, const unsigned char* row_mask /* may be NULL */, const double* K,
+                             int k_per_segment, double reproj_thresh, int max_iters, double confidence, double* pose,
+                             int* found, int* n_inliers, unsigned char* inlier_mask /* may be NULL */);
+
 /* ---- lens undistortion: images and point rows (the calls in front of the chain) ----
  * dst = cv::undistort(src, K, dist, newK) with INTER_LINEAR and BORDER_CONSTANT 0,
  * and cv::undistortPoints(src, dst, K, dist, noArray(), P), for OpenCV's

@@ -516,6 +516,29 @@ int pose_device(sift_ctx* c, const float* src_xy, const float* dst_xy, const int
   return SIFT_OK;
 }
 
+// ---- a whole batch: solvePnPRansac per segment of 3-D / 2-D rows ----
+int check_pnp(sift_ctx* c, const double* xyz, const float* xy, const int* m_offsets, int n_segments, int m_cap,
+              const double* K, int k_per_segment, const double* pose, const int* found, const int* n_inliers) {
+  if (!c) return SIFT_E_INVALID;
+  if (n_segments < 0 || m_cap < 0) return fail(c, SIFT_E_INVALID, "negative count");
+  if (k_per_segment != 0 && k_per_segment != 1) return fail(c, SIFT_E_INVALID, "k_per_segment must be 0 or 1");
+  if (n_segments == 0 || m_cap == 0) return SIFT_OK;
+  if (!xyz || !xy || !m_offsets || !K || !pose || !found || !n_inliers) return fail(c, SIFT_E_INVALID, "null buffer");
+  return SIFT_OK;
+}
+
+int pnp_device(sift_ctx* c, const double* xyz, const float* xy, const int* moff, int n_segments, int m_cap,
+               const unsigned char* row_mask, const double* K, int k_per_segment, double thr, int max_iters,
+               double confidence, double* pose, int* found, int* n_inliers, unsigned char* mask_out) {
+  {
+    StageScope sc(c, ST_PNP_SEG);  // the work depends on offsets and rows only the device knows
+    launch_pnp_seg(c->stream, xyz, xy, moff, n_segments, m_cap, row_mask, K, k_per_segment, thr, max_iters, confidence,
+                   pose, found, n_inliers, mask_out);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
 // ---- readImage front end, src/main.cpp:79-87 ----
 int check_bgr(sift_ctx* c, const void* bgr, int batch, int rows, int cols, int out_rows, int out_cols,
               const void* gray) {
@@ -1261,6 +1284,74 @@ int sift_triangulate_points_segmented_device(sift_ctx* c, const float* d_src_xy,
     launch_triangulate_seg(c->stream, d_src_xy, d_dst_xy, d_m_offsets, n_segments, m_cap, d_P_src, d_P_dst, d_xyzw);
   }
   HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
+// ---- solveP3P / solvePnPRansac: one row set on the host, a batch on the device ----
+int sift_solve_p3p(const double* xyz, const float* xy, const double* K, double* poses, int* n_solutions) {
+  if (!xyz || !xy || !K || !poses || !n_solutions) return SIFT_E_INVALID;
+  *n_solutions = solve_p3p(xyz, xy, K, poses);
+  return SIFT_OK;
+}
+
+int sift_solve_pnp(const double* xyz, const float* xy, int n, const unsigned char* row_mask, const double* K,
+                   double reproj_thresh, int max_iters, double confidence, double* pose, unsigned char* inlier_mask,
+                   int* n_inliers) {
+  if (!K || !pose || !n_inliers || n < 0 || (n > 0 && (!xyz || !xy))) return SIFT_E_INVALID;
+  // none: solve_pnp_ransac has zeroed every output
+  return solve_pnp_ransac(xyz, xy, n, row_mask, K, reproj_thresh, max_iters, confidence, pose, inlier_mask, n_inliers)
+             ? SIFT_OK
+             : SIFT_E_INVALID;
+}
+
+int sift_solve_pnp_segmented_device(sift_ctx* c, const double* d_xyz, const float* d_xy, const int* d_m_offsets,
+                                    int n_segments, int m_cap, const unsigned char* d_row_mask, const double* d_K,
+                                    int k_per_segment, double reproj_thresh, int max_iters, double confidence,
+                                    double* d_pose, int* d_found, int* d_n_inliers, unsigned char* d_inlier_mask) {
+  int rc = check_pnp(c, d_xyz, d_xy, d_m_offsets, n_segments, m_cap, d_K, k_per_segment, d_pose, d_found, d_n_inliers);
+  if (rc || n_segments == 0 || m_cap == 0) return rc;
+  (void)hipSetDevice(c->device);
+  return pnp_device(c, d_xyz, d_xy, d_m_offsets, n_segments, m_cap, d_row_mask, d_K, k_per_segment, reproj_thresh,
+                    max_iters, confidence, d_pose, d_found, d_n_inliers, d_inlier_mask);
+}
+
+int sift_solve_pnp_segmented(sift_ctx* c, const double* xyz, const float* xy, const int* m_offsets, int n_segments,
+                             int m_cap, const unsigned char* row_mask, const double* K, int k_per_segment,
+                             double reproj_thresh, int max_iters, double confidence, double* pose, int* found,
+                             int* n_inliers, unsigned char* inlier_mask) {
+  int rc = check_pnp(c, xyz, xy, m_offsets, n_segments, m_cap, K, k_per_segment, pose, found, n_inliers);
+  if (rc || n_segments == 0 || m_cap == 0) return rc;
+  (void)hipSetDevice(c->device);
+  PnpHost S;
+  if ((rc = carve(c, &S, [&](Carver& a) { return pnp_host_layout(a, n_segments, m_cap, k_per_segment); }))) return rc;
+  const size_t ob = (size_t)(n_segments + 1) * sizeof(int);
+  const size_t kb = (k_per_segment ? (size_t)n_segments : 1) * 9 * sizeof(double);
+  int lo = m_cap, hi = 0;  // the span the segments' rows lie in, backwards and overlapping ones included
+  for (int b = 0; b <= n_segments; ++b) {
+    const int v = clamp_off(m_offsets[b], m_cap);
+    lo = v < lo ? v : lo;
+    hi = v > hi ? v : hi;
+  }
+  HIP_TRY(c, hipMemcpyAsync(S.xyz, xyz, (size_t)m_cap * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.xy, xy, (size_t)m_cap * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.m_off, m_offsets, ob, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S.K, K, kb, hipMemcpyHostToDevice, c->stream));
+  if (row_mask) HIP_TRY(c, hipMemcpyAsync(S.row_mask, row_mask, (size_t)m_cap, hipMemcpyHostToDevice, c->stream));
+  // bytes of [lo, hi) that no segment owns (offsets that skip rows) go out and come back as they are
+  if (inlier_mask && hi > lo)
+    HIP_TRY(c, hipMemcpyAsync(S.mask + lo, inlier_mask + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, c->stream));
+  if ((rc = pnp_device(c, S.xyz, S.xy, S.m_off, n_segments, m_cap, row_mask ? S.row_mask : nullptr, S.K, k_per_segment,
+                       reproj_thresh, max_iters, confidence, S.pose, S.found, S.n_inliers,
+                       inlier_mask ? S.mask : nullptr)))
+    return rc;
+  HIP_TRY(c, hipMemcpyAsync(pose, S.pose, (size_t)n_segments * 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(found, S.found, (size_t)n_segments * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(n_inliers, S.n_inliers, (size_t)n_segments * sizeof(int), hipMemcpyDeviceToHost,
+                            c->stream));
+  // only the segments' mask bytes come back: the others are left untouched, as in the device form
+  if (inlier_mask && hi > lo)
+    HIP_TRY(c, hipMemcpyAsync(inlier_mask + lo, S.mask + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return SIFT_OK;
 }
 

@@ -333,6 +333,17 @@ void launch_recover_pose_seg(hipStream_t st, const float* src_xy, const float* d
                              double* E, int* pose_found, int* n_good, unsigned char* mask_out, double* xyz);
 void launch_triangulate_seg(hipStream_t st, const float* src_xy, const float* dst_xy, const int* moff, int n_segments,
                             int m_cap, const double* P_src, const double* P_dst, double* xyzw);
+// pnp.hip: solveP3P (up to four poses, returns their number) and solvePnPRansac on the host; xyz is [n][3]
+// doubles, xy [n][2] floats, a pose [R | t] row-major (12); row_mask and mask_out may be null.
+int solve_p3p(const double* xyz, const float* xy, const double* K, double* poses);
+int solve_pnp_ransac(const double* xyz, const float* xy, int n, const unsigned char* row_mask, const double* K,
+                     double thr, int max_iters, double confidence, double* pose, unsigned char* mask_out,
+                     int* n_inliers);
+// pnp_batch.hip: the same per segment; one workgroup each, no scratch.  K is one 3x3 (k_per_segment 0) or
+// [n_segments][9]; pose is [n_segments][12].
+void launch_pnp_seg(hipStream_t st, const double* xyz, const float* xy, const int* moff, int n_segments, int m_cap,
+                    const unsigned char* row_mask, const double* K, int k_per_segment, double thr, int max_iters,
+                    double confidence, double* pose, int* found, int* n_inliers, unsigned char* mask_out);
 // sift_selftest_math ops 8 / 9: out[i] = update_num_iters(confidence, (good[i] of n[i] pairs), 4, 2000)
 void launch_update_num_iters_selftest(hipStream_t st, double confidence, const float* good, const float* n, float* out,
                                       int count);

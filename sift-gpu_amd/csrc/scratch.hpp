@@ -413,6 +413,28 @@ inline PoseHost pose_host_layout(Carver& a, int n_segments, int m_cap, int k_per
           a.take<double>((size_t)m_cap * 3)};
 }
 
+// ---- absolute pose from 3-D / 2-D rows (pnp_batch.hip) ----
+// sift_solve_pnp_segmented_device carves nothing: a round is kPnpRound
+// hypotheses, one P3P solve per thread of the segment's workgroup; a round's
+// subsets (4 rows each) and inlier counts live in LDS beside the refit's 64 x 28
+// terms (20 KB in all), the hypotheses in registers.
+#ifndef SIFT_PNP_ROUND
+#define SIFT_PNP_ROUND 256
+#endif
+constexpr int kPnpRound = SIFT_PNP_ROUND;
+// sift_solve_pnp_segmented stages the rows read (3-D points, pixels, the row
+// mask), the offsets and the calibrations, then the results.
+struct PnpHost {
+  double* xyz; float* xy; int* m_off; unsigned char* row_mask; double *K, *pose; int *found, *n_inliers;
+  unsigned char* mask;
+};
+inline PnpHost pnp_host_layout(Carver& a, int n_segments, int m_cap, int k_per_segment) {
+  return {a.take<double>((size_t)m_cap * 3), a.take<float>((size_t)m_cap * 2), a.take<int>((size_t)n_segments + 1),
+          a.take<unsigned char>((size_t)m_cap), a.take<double>(k_per_segment ? (size_t)n_segments * 9 : 9),
+          a.take<double>((size_t)n_segments * 12), a.take<int>((size_t)n_segments), a.take<int>((size_t)n_segments),
+          a.take<unsigned char>((size_t)m_cap)};
+}
+
 // ---- lens undistortion (undistort.hip) ----
 // The device forms carve nothing.  sift_undistort stages one image, its camera
 // (K, the eight coefficients, newK) and the result; sift_undistort_points_segmented

@@ -191,6 +191,12 @@ def lib():
                                                  ctypes.c_double, pdbl, pdbl, pint, pint, vp, vp]),
             "sift_triangulate_points": (ip, [pdbl, pdbl, fp, fp, ip, pdbl]),
             "sift_triangulate_points_segmented_device": (ip, [vp, vp, vp, vp, ip, ip, vp, vp, vp]),
+            "sift_solve_p3p": (ip, [pdbl, fp, pdbl, pdbl, pint]),
+            "sift_solve_pnp": (ip, [pdbl, fp, ip, vp, pdbl, ctypes.c_double, ip, ctypes.c_double, pdbl, vp, pint]),
+            "sift_solve_pnp_segmented_device": (ip, [vp, vp, vp, vp, ip, ip, vp, vp, ip, ctypes.c_double, ip,
+                                                     ctypes.c_double, vp, vp, vp, vp]),
+            "sift_solve_pnp_segmented": (ip, [vp, pdbl, fp, pint, ip, ip, vp, pdbl, ip, ctypes.c_double, ip,
+                                              ctypes.c_double, pdbl, pint, pint, vp]),
             "sift_undistort_batch_device": (ip, [vp, ip, ip, vp, ip, ip, sz, sz, vp, vp, vp, ip, ip, vp, ip, ip, sz, sz]),
             "sift_undistort": (ip, [vp, ip, ip, vp, ip, ip, sz, pdbl, pdbl, pdbl, vp, ip, ip]),
             "sift_undistort_points": (ip, [pdbl, pdbl, pdbl, ip, vp, vp, sz, ip]),
@@ -229,7 +235,8 @@ def lib():
                     "sift_recover_pose_segmented_device", "sift_recover_pose_segmented", "sift_triangulate_points",
                     "sift_triangulate_points_segmented_device", "sift_undistort_batch_device", "sift_undistort",
                     "sift_undistort_points", "sift_undistort_points_segmented_device",
-                    "sift_undistort_points_segmented"}  # absent from older builds (A/B runs against a saved library)
+                    "sift_undistort_points_segmented", "sift_solve_p3p", "sift_solve_pnp",
+                    "sift_solve_pnp_segmented_device", "sift_solve_pnp_segmented"}  # absent from older builds (A/B runs against a saved library)
         for name, (res, args) in sigs.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -1329,6 +1336,66 @@ class Context:
                         self.h, vp(src_xy_ptr), vp(dst_xy_ptr), vp(m_offsets_ptr), n_segments, m_cap, vp(P_src_ptr),
                         vp(P_dst_ptr), vp(xyzw_ptr)))
 
+    # ---- a whole batch: absolute pose per segment from 3-D / 2-D rows (PnP RANSAC over P3P) ---
+    def solve_pnp_segmented_device(self, xyz_ptr: int, xy_ptr: int, m_offsets_ptr: int, n_segments: int, m_cap: int,
+                                   K_ptr: int, pose_ptr: int, found_ptr: int, n_inliers_ptr: int,
+                                   k_per_segment: int = 0, row_mask_ptr: int | None = None,
+                                   reprojectionError: float = 8.0, iterationsCount: int = 100,
+                                   confidence: float = 0.99, inlier_mask_ptr: int | None = None):
+        """Device-pointer form (no sync) of solvePnPRansac for every segment
+        [m_offsets[b], m_offsets[b+1]) of the rows: xyz_ptr [m_cap][3] float64 and
+        row_mask_ptr [m_cap] uint8 (or None) exactly as
+        recover_pose_segmented_device leaves xyz_ptr / mask_out_ptr, xy_ptr
+        [m_cap][2] float32 pixels of the view to register, K_ptr one 3x3 float64
+        (k_per_segment 0) or [n_segments][9] (1); pose_ptr [n_segments][12]
+        float64 ([R | t] by rows, X_cam = R X + t), found_ptr and n_inliers_ptr
+        [n_segments] int32, inlier_mask_ptr [m_cap] uint8 or None."""
+        vp = lambda p: ctypes.c_void_p(p or None)  # noqa: E731
+        self._check("sift_solve_pnp_segmented_device",
+                    self._L.sift_solve_pnp_segmented_device(
+                        self.h, vp(xyz_ptr), vp(xy_ptr), vp(m_offsets_ptr), n_segments, m_cap, vp(row_mask_ptr),
+                        vp(K_ptr), int(k_per_segment), float(reprojectionError), int(iterationsCount),
+                        float(confidence), vp(pose_ptr), vp(found_ptr), vp(n_inliers_ptr), vp(inlier_mask_ptr)))
+
+    def solvePnPBatch(self, objectPoints, imagePoints, m_offsets, K, reprojectionError: float = 8.0,
+                      iterationsCount: int = 100, confidence: float = 0.99, row_mask=None):
+        """solvePnPRansac for every segment at once (host arrays): objectPoints
+        [n, 3], imagePoints [n, 2], K one 3x3 or [n_segments, 3, 3], row_mask [n]
+        or None -> a list of (R 3x3, t 3, mask uint8[segment's rows], n_inliers)
+        per segment, R = t = None where the segment has no model; offsets clamped
+        to the number of rows."""
+        X = np.ascontiguousarray(objectPoints, np.float64).reshape(-1, 3)
+        p = np.ascontiguousarray(imagePoints, np.float32).reshape(-1, 2)
+        mo = np.ascontiguousarray(m_offsets, np.int32)
+        if len(X) != len(p) or mo.ndim != 1 or len(mo) < 1:
+            raise ValueError("objectPoints [n, 3] / imagePoints [n, 2] and m_offsets n_segments + 1 entries")
+        nseg, n = len(mo) - 1, len(X)
+        Ka = np.ascontiguousarray(K, np.float64).reshape(-1, 9)
+        per = 0 if len(Ka) == 1 else 1
+        if per and len(Ka) != nseg:
+            raise ValueError("K must be one 3x3 or [n_segments, 3, 3]")
+        mi = None if row_mask is None else np.ascontiguousarray(row_mask, np.uint8).reshape(-1)
+        if mi is not None and len(mi) != n:
+            raise ValueError("row_mask must have one byte per row")
+        pose = np.zeros((nseg, 12), np.float64)
+        fo, ni = np.zeros(nseg, np.int32), np.zeros(nseg, np.int32)
+        mout = np.zeros(n, np.uint8)
+        pint, pdbl = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)
+        self._check("sift_solve_pnp_segmented",
+                    self._L.sift_solve_pnp_segmented(
+                        self.h, X.ctypes.data_as(pdbl), _fp(p), mo.ctypes.data_as(pint), nseg, n,
+                        None if mi is None else mi.ctypes.data, Ka.ctypes.data_as(pdbl), per,
+                        float(reprojectionError), int(iterationsCount), float(confidence), pose.ctypes.data_as(pdbl),
+                        fo.ctypes.data_as(pint), ni.ctypes.data_as(pint), mout.ctypes.data))
+        o = np.clip(mo.astype(np.int64), 0, n)
+        out = []
+        for b in range(nseg):
+            rows = slice(o[b], max(o[b], o[b + 1]))
+            P = pose[b].reshape(3, 4)
+            out.append((P[:, :3].copy() if fo[b] else None, P[:, 3].copy() if fo[b] else None, mout[rows].copy(),
+                        int(ni[b])))
+        return out
+
     # ---- device batch API ------------------------------------------------
     def synth_images(self, out_ptr: int, batch: int, rows: int, cols: int, row_stride: int,
                      img_stride: int, seed_base: int = 0):
@@ -1911,6 +1978,54 @@ def triangulatePoints(P_src, P_dst, src, dst):
     if rc != SIFT_OK:
         raise SiftError("sift_triangulate_points", rc, "bad argument")
     return out[:len(s)]
+
+
+def solveP3P(objectPoints, imagePoints, K):
+    """cv::solveP3P for three 3-D points and their pixels -> a list of up to four (R 3x3, t 3),
+    X_cam = R X + t, in the library's fixed order.  Host code in the library (pnp.hip;
+    include/sift_hip.h has the rule)."""
+    X = np.ascontiguousarray(objectPoints, np.float64).reshape(-1, 3)
+    p = np.ascontiguousarray(imagePoints, np.float32).reshape(-1, 2)
+    if len(X) != 3 or len(p) != 3:
+        raise ValueError("solveP3P takes exactly three rows")
+    Ka = np.ascontiguousarray(K, np.float64).reshape(9)
+    poses = np.zeros((4, 12), np.float64)
+    ns = ctypes.c_int(0)
+    pdbl = ctypes.POINTER(ctypes.c_double)
+    rc = lib().sift_solve_p3p(X.ctypes.data_as(pdbl), _fp(p), Ka.ctypes.data_as(pdbl), poses.ctypes.data_as(pdbl),
+                              ctypes.byref(ns))
+    if rc != SIFT_OK:
+        raise SiftError("sift_solve_p3p", rc, "bad argument")
+    return [(poses[k].reshape(3, 4)[:, :3].copy(), poses[k].reshape(3, 4)[:, 3].copy()) for k in range(ns.value)]
+
+
+def solvePnPRansac(objectPoints, imagePoints, K, reprojectionError: float = 8.0, iterationsCount: int = 100,
+                   confidence: float = 0.99, row_mask=None):
+    """cv::solvePnPRansac(objectPoints, imagePoints, K, noArray(), ..., SOLVEPNP_P3P) on undistorted
+    pixels -> (R 3x3, t 3, mask uint8[n], n_inliers), X_cam = R X + t; R = t = None when there is no
+    model.  row_mask [n] (or None) takes rows out, as recoverPose's mask does.  Host code in the library."""
+    X = np.ascontiguousarray(objectPoints, np.float64).reshape(-1, 3)
+    p = np.ascontiguousarray(imagePoints, np.float32).reshape(-1, 2)
+    if len(X) != len(p):
+        raise ValueError("point counts differ")
+    n = len(X)
+    Ka = np.ascontiguousarray(K, np.float64).reshape(9)
+    mi = None if row_mask is None else np.ascontiguousarray(row_mask, np.uint8).reshape(-1)
+    if mi is not None and len(mi) != n:
+        raise ValueError("row_mask must have one byte per row")
+    pose = np.zeros(12, np.float64)
+    mout = np.zeros(max(n, 1), np.uint8)
+    Xs = X if n else np.zeros((1, 3), np.float64)
+    ps = p if n else np.zeros((1, 2), np.float32)
+    ni = ctypes.c_int(0)
+    pdbl = ctypes.POINTER(ctypes.c_double)
+    rc = lib().sift_solve_pnp(Xs.ctypes.data_as(pdbl), _fp(ps), n, None if mi is None else mi.ctypes.data,
+                              Ka.ctypes.data_as(pdbl), float(reprojectionError), int(iterationsCount),
+                              float(confidence), pose.ctypes.data_as(pdbl), mout.ctypes.data, ctypes.byref(ni))
+    if rc != SIFT_OK:
+        return None, None, np.zeros(n, np.uint8), 0
+    P = pose.reshape(3, 4)
+    return P[:, :3].copy(), P[:, 3].copy(), mout[:n], ni.value
 
 
 WARP_INVERSE_MAP = 16  # cv::WARP_INVERSE_MAP

@@ -1370,6 +1370,102 @@ int sift_solve_pnp_segmented(sift_ctx* ctx, const double* xyz, const float* xy, 
                              int k_per_segment, double reproj_thresh, int max_iters, double confidence, double* pose,
                              int* found, int* n_inliers, unsigned char* inlier_mask /* may be NULL */);
 
+/* ---- the join of two match tables on a shared keypoint: 2-D / 3-D rows (join.hip) ----
+ * sift_solve_pnp* wants row i of xyz to belong to row i of xy.  sift_recover_pose*
+ * leaves xyz by pair row of the table between views b and b + 1; the next view's
+ * pixels sit in another table, between b + 1 and b + 2, with other rows in another
+ * order.  The two tables share the keypoints of view b + 1, and this call joins
+ * them on that keypoint's index.  The rule for one segment:
+ * Table A is na records with a_xyz ([na][3] doubles) and a_mask (na bytes, may be
+ * NULL), exactly as sift_recover_pose* leaves xyz and mask_out.  Table B is nb
+ * records with b_mask (nb bytes, may be NULL) and b_xy ([nb][2] floats), the new
+ * view's pixel per record: the src_xy or dst_xy the ratio stage gathered.
+ * a_key_side and b_key_side say which index of a record names the shared view's
+ * keypoint, its query (SIFT_JOIN_QUERY) or its train (SIFT_JOIN_TRAIN); n_keys is
+ * the shared view's keypoint count.  A record's segment field is not read.
+ * 1. An A row is a candidate iff its mask byte is non-zero (or the mask is NULL),
+ *    its key lies in [0, n_keys) and distance >= 0 (false for NaN).
+ * 2. Among the candidates of one key the winner has the smallest
+ *    ((uint64)bits(distance + 0.0f) << 32) | row: the smallest distance (-0.0 counts
+ *    as 0, +inf is the largest), then the lowest row.  A ratio table may name one
+ *    train keypoint from several queries; this decides between them.
+ * 3. A B row joins iff its mask byte is non-zero (or the mask is NULL), its key lies
+ *    in [0, n_keys) and that key has a winner.  Several B rows may join one A row.
+ * 4. Joined B rows are written densely in B's row order: xyz_out[j] = a_xyz[winner]
+ *    (three doubles copied bit for bit), xy_out[j] = b_xy[row], a_row[j] = winner,
+ *    b_row[j] = row -- row indices into the caller's arrays, with which a caller
+ *    extends its tracks.  b_joined[row] is 1 iff B row `row` joined, else 0, for
+ *    every B row: its complement is the set of pairs to triangulate once the new
+ *    view's pose is known.  Every output may be NULL; xyz_out needs a_xyz and
+ *    xy_out needs b_xy.
+ * No floating arithmetic beyond the + 0.0f.  Returns the number of joined rows (at
+ * most nb, the capacity the row outputs need), or SIFT_E_INVALID for NULL records
+ * with a count > 0, a negative count or a side outside {0, 1}.  Host code, no
+ * context; pinned bit for bit against tests/join_oracle.py. */
+#define SIFT_JOIN_QUERY 0
+#define SIFT_JOIN_TRAIN 1
+int sift_join_matches(const sift_match* a, int na, int a_key_side, const unsigned char* a_mask /* may be NULL */,
+                      const double* a_xyz /* [na][3] */, const sift_match* b, int nb, int b_key_side,
+                      const unsigned char* b_mask /* may be NULL */, const float* b_xy /* [nb][2] */, int n_keys,
+                      double* xyz_out, float* xy_out, int* a_row, int* b_row, unsigned char* b_joined);
+
+/* The same for every segment of a batch, on the device in stream order, with the
+ * row contract of sift_find_fundamental_segmented_device on each of three offset
+ * arrays (n_segments + 1 ints each, read on the device, never by the host):
+ * segment s takes A rows [clamp(a_offsets[s]), clamp(a_offsets[s+1])) of d_a /
+ * d_a_mask / d_a_xyz clamped to a_cap, B rows from d_b_offsets in the same way
+ * clamped to b_cap (a backwards pair is an empty segment), and n_keys =
+ * clamp(key_offsets[s+1]) - clamp(key_offsets[s]) clamped to key_cap, the total
+ * keypoint count of the shared views; its winners live in entries
+ * [clamp(key_offsets[s]), + n_keys) of a lookup of key_cap entries.  Each segment
+ * gets exactly what sift_join_matches gives for its rows, with a_row and b_row
+ * absolute rows of d_a and d_b.  Segment s's joined rows are [j_offsets[s],
+ * j_offsets[s+1]) of d_xyz_out ([j_cap][3]), d_xy_out ([j_cap][2]), d_a_row and
+ * d_b_row ([j_cap]), in segment order (an ordered scan, no atomics); d_j_offsets is
+ * n_segments + 1 ints and its last entry is the true total; only the first j_cap
+ * rows are written (j_cap = b_cap always suffices).  d_b_joined is [b_cap] bytes by
+ * B row; bytes outside the segments' B rows are never written.  d_xyz_out, d_xy_out,
+ * d_a_row, d_b_row, d_b_joined, the masks, d_a_xyz and d_b_xy may be NULL as above.
+ * The record tables must be 16-byte aligned.  The inputs are only read, and may
+ * alias each other.
+ * Consecutive frames, one table and no copy: with d_matches / d_dst_xy / d_m_offsets
+ * from sift_ratio_matches_device over the batch - 1 pairs of a batch matched as
+ * sift_knn_match_l1_segmented_device describes (pair b: query = view b, train =
+ * view b + 1), d_xyz / d_mask_out from sift_recover_pose_segmented_device on them
+ * and d_img_offsets the batch's keypoint offsets, pass d_a = d_b = d_matches,
+ * d_a_offsets = d_m_offsets, d_b_offsets = d_m_offsets + 1, a_cap = b_cap = m_cap,
+ * a_key_side = SIFT_JOIN_TRAIN (view b + 1 is pair b's train), b_key_side =
+ * SIFT_JOIN_QUERY (and pair b + 1's query), d_a_mask = d_mask_out, d_a_xyz = d_xyz,
+ * d_b_mask = NULL, d_b_xy = d_dst_xy (view b + 2 is pair b + 1's train),
+ * d_key_offsets = d_img_offsets + 1, n_segments = batch - 2.  d_xyz_out, d_xy_out and
+ * d_j_offsets then go straight into sift_solve_pnp_segmented_device as d_xyz, d_xy
+ * and d_m_offsets with d_row_mask = NULL.
+ * Enqueued on the context stream, no synchronisation and no host value read; the
+ * scratch (the lookup, two tables of n_segments + 1 ints and one count per 256 B
+ * rows) is the context's one block, which grows, with a wait, only when a call
+ * needs more than any call before it.  A NULL context: SIFT_E_INVALID.  A negative
+ * count or a side outside {0, 1}: SIFT_E_INVALID.  n_segments == 0: SIFT_OK, nothing
+ * enqueued.  A NULL required buffer (the offsets, d_j_offsets, a table with a
+ * capacity > 0): SIFT_E_INVALID, nothing enqueued.  b_cap == 0: d_j_offsets is all
+ * zeros.  Key slices that overlap because key_offsets decreases give unspecified
+ * rows, and row ranges of one table that overlap (offsets that fall and rise
+ * again) are joined only as far as cap / 256 + n_segments blocks of 256 rows reach
+ * (d_j_offsets counts what was joined); every access stays in bounds. */
+int sift_join_matches_segmented_device(sift_ctx* ctx, const sift_match* d_a, const int* d_a_offsets, int a_cap,
+                                       int a_key_side, const unsigned char* d_a_mask /* may be NULL */,
+                                       const double* d_a_xyz, const sift_match* d_b, const int* d_b_offsets, int b_cap,
+                                       int b_key_side, const unsigned char* d_b_mask /* may be NULL */,
+                                       const float* d_b_xy, const int* d_key_offsets, int key_cap, int n_segments,
+                                       double* d_xyz_out, float* d_xy_out, int* d_a_row, int* d_b_row,
+                                       unsigned char* d_b_joined, int j_cap, int* d_j_offsets);
+/* Host buffers (synchronous); the tables have a_cap / b_cap rows, the row outputs j_cap: */
+int sift_join_matches_segmented(sift_ctx* ctx, const sift_match* a, const int* a_offsets, int a_cap, int a_key_side,
+                                const unsigned char* a_mask /* may be NULL */, const double* a_xyz,
+                                const sift_match* b, const int* b_offsets, int b_cap, int b_key_side,
+                                const unsigned char* b_mask /* may be NULL */, const float* b_xy,
+                                const int* key_offsets, int key_cap, int n_segments, double* xyz_out, float* xy_out,
+                                int* a_row, int* b_row, unsigned char* b_joined, int j_cap, int* j_offsets);
+
 /* ---- lens undistortion: images and point rows (the calls in front of the chain) ----
  * dst = cv::undistort(src, K, dist, newK) with INTER_LINEAR and BORDER_CONSTANT 0,
  * and cv::undistortPoints(src, dst, K, dist, noArray(), P), for OpenCV's

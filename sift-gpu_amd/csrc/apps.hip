@@ -6,7 +6,7 @@
 // homography wrappers, the segmented homography and corner transform, the
 // affine / similarity estimate and the fundamental matrix (each one pair set
 // and segmented; fundamental.hip, fundamental_batch.hip), and the
-// perspective warp of a batch.  Host code only; the kernels live in match.hip,
+// perspective warp of a batch, and the join of two match tables (join.hip, join_rule.hpp).  Host code only; the kernels live in match.hip,
 // match_u8.hip, match_l2_u8.hip, match_l2_f32.hip, match_window.hip, match_epipolar.hip, cross_check.hip,
 // frontend.hip, upsample.hip, homography_batch.hip, affine_batch.hip and warp.hip (the one-pair
 // homography and affine estimate are host code in homography.hip and affine.hip).  The segmented matchers are one path, written once as
@@ -16,6 +16,7 @@
 #include <cstring>
 
 #include "ctx.hpp"
+#include "join_rule.hpp"
 #include "scratch.hpp"
 #include "undistort_math.hpp"
 #include "warp_math.hpp"
@@ -534,6 +535,43 @@ int pnp_device(sift_ctx* c, const double* xyz, const float* xy, const int* moff,
     StageScope sc(c, ST_PNP_SEG);  // the work depends on offsets and rows only the device knows
     launch_pnp_seg(c->stream, xyz, xy, moff, n_segments, m_cap, row_mask, K, k_per_segment, thr, max_iters, confidence,
                    pose, found, n_inliers, mask_out);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SIFT_OK;
+}
+
+// ---- a whole batch: the join of two record tables on a shared keypoint (join.hip) ----
+bool join_side_ok(int side) { return side == SIFT_JOIN_QUERY || side == SIFT_JOIN_TRAIN; }
+
+// One call's buffers, device or host pointers alike.
+struct JoinCall {
+  const sift_match* a; const int* a_off; int a_cap, a_side; const unsigned char* a_mask; const double* a_xyz;
+  const sift_match* b; const int* b_off; int b_cap, b_side; const unsigned char* b_mask; const float* b_xy;
+  const int* key_off; int key_cap, n_segments;
+  double* xyz_out; float* xy_out; int *a_row, *b_row; unsigned char* b_joined; int j_cap; int* j_off;
+};
+
+int check_join(sift_ctx* c, const JoinCall& J) {
+  if (!c) return SIFT_E_INVALID;
+  if (J.n_segments < 0 || J.a_cap < 0 || J.b_cap < 0 || J.key_cap < 0 || J.j_cap < 0)
+    return fail(c, SIFT_E_INVALID, "negative count");
+  if (!join_side_ok(J.a_side) || !join_side_ok(J.b_side))
+    return fail(c, SIFT_E_INVALID, "a key side must be SIFT_JOIN_QUERY or SIFT_JOIN_TRAIN");
+  if (J.n_segments == 0) return SIFT_OK;
+  if (!J.a_off || !J.b_off || !J.key_off || !J.j_off || (J.a_cap > 0 && !J.a) || (J.b_cap > 0 && !J.b))
+    return fail(c, SIFT_E_INVALID, "null buffer");
+  if ((J.xyz_out && !J.a_xyz) || (J.xy_out && !J.b_xy))
+    return fail(c, SIFT_E_INVALID, "null buffer: xyz_out needs a_xyz, xy_out needs b_xy");
+  return SIFT_OK;
+}
+
+int join_device(sift_ctx* c, const JoinCall& J, const JoinParts& P) {
+  {
+    StageScope sc(c, ST_JOIN);  // the work depends on offsets and keys only the device knows
+    launch_join_matches(c->stream, J.a, J.a_off, J.a_cap, J.a_side, J.a_mask, J.a_xyz, J.b, J.b_off, J.b_cap, J.b_side,
+                        J.b_mask, J.b_xy, J.key_off, J.key_cap, J.n_segments, J.xyz_out, J.xy_out, J.a_row, J.b_row,
+                        J.b_joined, J.j_cap, J.j_off, reinterpret_cast<unsigned long long*>(P.lookup), P.a_tiles,
+                        P.b_tiles, P.blk_scan);
   }
   HIP_TRY(c, hipGetLastError());
   return SIFT_OK;
@@ -1352,6 +1390,99 @@ int sift_solve_pnp_segmented(sift_ctx* c, const double* xyz, const float* xy, co
   if (inlier_mask && hi > lo)
     HIP_TRY(c, hipMemcpyAsync(inlier_mask + lo, S.mask + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SIFT_OK;
+}
+
+// ---- the join of two record tables: one segment on the host, a batch on the device ----
+int sift_join_matches(const sift_match* a, int na, int a_key_side, const unsigned char* a_mask, const double* a_xyz,
+                      const sift_match* b, int nb, int b_key_side, const unsigned char* b_mask, const float* b_xy,
+                      int n_keys, double* xyz_out, float* xy_out, int* a_row, int* b_row, unsigned char* b_joined) {
+  if (na < 0 || nb < 0 || n_keys < 0 || !join_side_ok(a_key_side) || !join_side_ok(b_key_side) || (na > 0 && !a) ||
+      (nb > 0 && !b) || (xyz_out && !a_xyz) || (xy_out && !b_xy))
+    return SIFT_E_INVALID;
+  return join_matches(a, na, a_key_side, a_mask, a_xyz, b, nb, b_key_side, b_mask, b_xy, n_keys, xyz_out, xy_out,
+                      a_row, b_row, b_joined);
+}
+
+int sift_join_matches_segmented_device(sift_ctx* c, const sift_match* d_a, const int* d_a_offsets, int a_cap,
+                                       int a_key_side, const unsigned char* d_a_mask, const double* d_a_xyz,
+                                       const sift_match* d_b, const int* d_b_offsets, int b_cap, int b_key_side,
+                                       const unsigned char* d_b_mask, const float* d_b_xy, const int* d_key_offsets,
+                                       int key_cap, int n_segments, double* d_xyz_out, float* d_xy_out, int* d_a_row,
+                                       int* d_b_row, unsigned char* d_b_joined, int j_cap, int* d_j_offsets) {
+  const JoinCall J{d_a, d_a_offsets, a_cap, a_key_side, d_a_mask, d_a_xyz, d_b, d_b_offsets, b_cap, b_key_side, d_b_mask,
+                   d_b_xy, d_key_offsets, key_cap, n_segments, d_xyz_out, d_xy_out, d_a_row, d_b_row, d_b_joined, j_cap,
+                   d_j_offsets};
+  int rc = check_join(c, J);
+  if (rc || n_segments == 0) return rc;
+  if (!aligned16(d_a, d_b)) return fail(c, SIFT_E_INVALID, "record tables must be 16-byte aligned");
+  (void)hipSetDevice(c->device);
+  if (b_cap == 0) {  // no B rows: nothing joins, and no byte of d_b_joined belongs to a segment
+    HIP_TRY(c, hipMemsetAsync(d_j_offsets, 0, (size_t)(n_segments + 1) * sizeof(int), c->stream));
+    return SIFT_OK;
+  }
+  JoinParts P;
+  if ((rc = carve(c, &P, [&](Carver& s) { return join_layout(s, n_segments, key_cap, b_cap); }))) return rc;
+  return join_device(c, J, P);
+}
+
+int sift_join_matches_segmented(sift_ctx* c, const sift_match* a, const int* a_offsets, int a_cap, int a_key_side,
+                                const unsigned char* a_mask, const double* a_xyz, const sift_match* b,
+                                const int* b_offsets, int b_cap, int b_key_side, const unsigned char* b_mask,
+                                const float* b_xy, const int* key_offsets, int key_cap, int n_segments,
+                                double* xyz_out, float* xy_out, int* a_row, int* b_row, unsigned char* b_joined,
+                                int j_cap, int* j_offsets) {
+  const JoinCall H{a, a_offsets, a_cap, a_key_side, a_mask, a_xyz, b, b_offsets, b_cap, b_key_side, b_mask, b_xy,
+                   key_offsets, key_cap, n_segments, xyz_out, xy_out, a_row, b_row, b_joined, j_cap, j_offsets};
+  int rc = check_join(c, H);
+  if (rc || n_segments == 0) return rc;
+  const size_t ob = (size_t)(n_segments + 1) * sizeof(int);
+  if (b_cap == 0) {
+    memset(j_offsets, 0, ob);
+    return SIFT_OK;
+  }
+  (void)hipSetDevice(c->device);
+  JoinHost S;
+  const JoinHostHas has{a_mask != nullptr, a_xyz != nullptr, b_mask != nullptr, b_xy != nullptr, xyz_out != nullptr,
+                        xy_out != nullptr, a_row != nullptr, b_row != nullptr, b_joined != nullptr};
+  if ((rc = carve(c, &S, [&](Carver& s) { return join_host_layout(s, n_segments, a_cap, b_cap, key_cap, j_cap, has); })))
+    return rc;
+  int lo = b_cap, hi = 0;  // the span the segments' B rows lie in, backwards and overlapping ones included
+  for (int s = 0; s <= n_segments; ++s) {
+    const int v = clamp_off(b_offsets[s], b_cap);
+    lo = v < lo ? v : lo;
+    hi = v > hi ? v : hi;
+  }
+  const hipStream_t st = c->stream;
+  if (a_cap) HIP_TRY(c, hipMemcpyAsync(S.a, a, (size_t)a_cap * sizeof(sift_match), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(S.a_off, a_offsets, ob, hipMemcpyHostToDevice, st));
+  if (a_mask && a_cap) HIP_TRY(c, hipMemcpyAsync(S.a_mask, a_mask, (size_t)a_cap, hipMemcpyHostToDevice, st));
+  if (a_xyz && a_cap)
+    HIP_TRY(c, hipMemcpyAsync(S.a_xyz, a_xyz, (size_t)a_cap * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(S.b, b, (size_t)b_cap * sizeof(sift_match), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(S.b_off, b_offsets, ob, hipMemcpyHostToDevice, st));
+  if (b_mask) HIP_TRY(c, hipMemcpyAsync(S.b_mask, b_mask, (size_t)b_cap, hipMemcpyHostToDevice, st));
+  if (b_xy) HIP_TRY(c, hipMemcpyAsync(S.b_xy, b_xy, (size_t)b_cap * 2 * sizeof(float), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(S.key_off, key_offsets, ob, hipMemcpyHostToDevice, st));
+  // bytes of [lo, hi) that no segment owns (offsets that skip rows) go out and come back as they are
+  if (b_joined && hi > lo)
+    HIP_TRY(c, hipMemcpyAsync(S.b_joined + lo, b_joined + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, st));
+  const JoinCall D{S.a, S.a_off, a_cap, a_key_side, S.a_mask, S.a_xyz, S.b, S.b_off, b_cap, b_key_side, S.b_mask, S.b_xy,
+                   S.key_off, key_cap, n_segments, S.xyz_out, S.xy_out, S.a_row, S.b_row, S.b_joined, j_cap, S.j_off};
+  if ((rc = join_device(c, D, S.parts))) return rc;
+  // the offsets come back first; then only the written rows
+  HIP_TRY(c, hipMemcpyAsync(j_offsets, S.j_off, ob, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  const size_t n = (size_t)(j_offsets[n_segments] < j_cap ? j_offsets[n_segments] : j_cap);
+  if (n) {
+    if (xyz_out) HIP_TRY(c, hipMemcpyAsync(xyz_out, S.xyz_out, n * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (xy_out) HIP_TRY(c, hipMemcpyAsync(xy_out, S.xy_out, n * 2 * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (a_row) HIP_TRY(c, hipMemcpyAsync(a_row, S.a_row, n * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (b_row) HIP_TRY(c, hipMemcpyAsync(b_row, S.b_row, n * sizeof(int), hipMemcpyDeviceToHost, st));
+  }
+  if (b_joined && hi > lo)
+    HIP_TRY(c, hipMemcpyAsync(b_joined + lo, S.b_joined + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
   return SIFT_OK;
 }
 

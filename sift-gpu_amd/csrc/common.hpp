@@ -410,6 +410,18 @@ void launch_cross_check(hipStream_t st, const int* idx, const float* dist, int f
                         int q_cap, const int* ridx, int rev_k, const int* toff, int t_cap, double ratio,
                         const sift_keypoint* q_kpts, const sift_keypoint* t_kpts, sift_match* matches, float* src_xy,
                         float* dst_xy, int m_cap, int* moff, int* blk_scan);
+// join.hip: the segmented, ordered join of two record tables on a shared keypoint
+// index (2-D / 3-D rows for sift_solve_pnp_segmented_device).  Both tables are
+// walked in join_max_blocks(cap, n_segments) blocks of 256 rows that never span
+// two segments.  Scratch: lookup [max(key_cap, 1)] uint64, a_tiles / b_tiles
+// [n_segments + 1] ints, blk_scan [join_max_blocks(b_cap, n_segments) + 1] ints.
+int join_max_blocks(int cap, int n_segments);
+void launch_join_matches(hipStream_t st, const sift_match* a, const int* aoff, int a_cap, int a_side,
+                         const unsigned char* a_mask, const double* a_xyz, const sift_match* b, const int* boff,
+                         int b_cap, int b_side, const unsigned char* b_mask, const float* b_xy, const int* koff,
+                         int key_cap, int n_segments, double* xyz_out, float* xy_out, int* a_row, int* b_row,
+                         unsigned char* b_joined, int j_cap, int* joff, unsigned long long* lookup, int* a_tiles,
+                         int* b_tiles, int* blk_scan);
 // match_window.hip: the spatially gated segmented matcher.  launch_window_bin
 // sorts the train keypoints of every grid (one per train segment, one in all
 // for a shared train set) into the cells of an nx x ny grid of side

@@ -65,7 +65,8 @@ class Buf {
   X(ST_WARP, "warp") X(ST_AFFINE_SEG, "affine_segmented")                                  \
   X(ST_MATCH_L2_F32, "match_l2sqr_f32_segmented") X(ST_FUND_SEG, "fundamental_segmented") \
   X(ST_MATCH_EPIPOLAR, "match_epipolar") X(ST_POSE_SEG, "recover_pose_segmented")          \
-  X(ST_TRI_SEG, "triangulate_segmented") X(ST_UNDISTORT, "undistort") X(ST_PNP_SEG, "pnp_segmented")
+  X(ST_TRI_SEG, "triangulate_segmented") X(ST_UNDISTORT, "undistort") X(ST_PNP_SEG, "pnp_segmented") \
+  X(ST_JOIN, "join_matches")
 enum Stage {
 #define X(id, name) id,
   SIFT_STAGES(X)

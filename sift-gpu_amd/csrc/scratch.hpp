@@ -1,12 +1,12 @@
 // scratch.hpp -- how the matcher, byte-matcher, windowed-matcher, epipolar-matcher, cross-check, front-end, segmented-homography and
-// segmented-affine entry points divide the context's one scratch block (sift_ctx::d_match).  Each
+// segmented-affine and match-join entry points divide the context's one scratch block (sift_ctx::d_match).  Each
 // layout is described once, as a function of a Carver, and run twice: on a null
 // base to measure the block, then on the block itself.  The four segmented
 // matchers share one host and one cross-match layout, templates over a metric
 // tag (L1F32, L1U8, L2SqrU8, L2SqrF32).  Plain host C++ (no HIP
 // include), so that tests/cpp/scratch_layout.cpp, match_u8_layout.cpp,
 // match_l2_u8_layout.cpp, match_l2_f32_layout.cpp, cross_check_layout.cpp, homography_layout.cpp, match_window_layout.cpp,
-// match_epipolar_layout.cpp and affine_layout.cpp check every layout without a GPU.
+// match_epipolar_layout.cpp, affine_layout.cpp and join_layout.cpp check every layout without a GPU.
 #pragma once
 
 #include <math.h>
@@ -23,7 +23,7 @@ class Carver {
  public:
   struct Piece { size_t off, bytes; };
   static constexpr size_t kAlign = 256;
-  static constexpr int kMaxPieces = 16;
+  static constexpr int kMaxPieces = 24;
   Piece pieces[kMaxPieces] = {};  // what was taken so far, for the layout test
   int n_pieces = 0;
 
@@ -433,6 +433,46 @@ inline PnpHost pnp_host_layout(Carver& a, int n_segments, int m_cap, int k_per_s
           a.take<unsigned char>((size_t)m_cap), a.take<double>(k_per_segment ? (size_t)n_segments * 9 : 9),
           a.take<double>((size_t)n_segments * 12), a.take<int>((size_t)n_segments), a.take<int>((size_t)n_segments),
           a.take<unsigned char>((size_t)m_cap)};
+}
+
+// ---- the join of two match tables on a shared keypoint (join.hip) ----
+// The stage walks each table in blocks of kJoinRows rows that never span two
+// segments, so a block has one segment and one key slice: tile tables like the
+// matchers' (entry s = the blocks of the segments before s, entry n_segments =
+// all of them), one per table.  join_max_tiles() is the most blocks a table's
+// capacity allows when its segments do not overlap, and the size of the grid.
+// sift_join_matches_segmented_device: the lookup (one uint64 per key of the
+// shared views, all ones = no winner), the two tile tables, then the block scan
+// of the B table's join_max_tiles() blocks.
+constexpr int kJoinRows = 256;
+inline int join_max_tiles(int cap, int n_segments) { return cap / kJoinRows + n_segments; }
+struct JoinParts { uint64_t* lookup; int *a_tiles, *b_tiles, *blk_scan; };
+inline JoinParts join_layout(Carver& a, int n_segments, int key_cap, int b_cap) {
+  const size_t offs = (size_t)n_segments + 1;
+  return {a.take<uint64_t>(at_least_one(key_cap)), a.take<int>(offs), a.take<int>(offs),
+          a.take<int>((size_t)join_max_tiles(b_cap, n_segments) + 1)};
+}
+
+// sift_join_matches_segmented: the staged tables (records, offsets, mask, the
+// rows gathered from: 3-D points of A, pixels of B), the key offsets and the
+// staged results, then the device form's pieces.  A buffer the caller left out
+// keeps its place and is null.
+struct JoinHost {
+  sift_match* a; int* a_off; unsigned char* a_mask; double* a_xyz;
+  sift_match* b; int* b_off; unsigned char* b_mask; float* b_xy; int* key_off;
+  double* xyz_out; float* xy_out; int *a_row, *b_row; unsigned char* b_joined; int* j_off; JoinParts parts;
+};
+struct JoinHostHas { bool a_mask, a_xyz, b_mask, b_xy, xyz_out, xy_out, a_row, b_row, b_joined; };
+inline JoinHost join_host_layout(Carver& a, int n_segments, int a_cap, int b_cap, int key_cap, int j_cap,
+                                 const JoinHostHas& has) {
+  const size_t offs = (size_t)n_segments + 1, na = at_least_one(a_cap), nb = at_least_one(b_cap),
+               nj = at_least_one(j_cap);
+  return {a.take<sift_match>(na), a.take<int>(offs), a.take_if<unsigned char>(has.a_mask, na),
+          a.take_if<double>(has.a_xyz, na * 3), a.take<sift_match>(nb), a.take<int>(offs),
+          a.take_if<unsigned char>(has.b_mask, nb), a.take_if<float>(has.b_xy, nb * 2), a.take<int>(offs),
+          a.take_if<double>(has.xyz_out, nj * 3), a.take_if<float>(has.xy_out, nj * 2), a.take_if<int>(has.a_row, nj),
+          a.take_if<int>(has.b_row, nj), a.take_if<unsigned char>(has.b_joined, nb), a.take<int>(offs),
+          join_layout(a, n_segments, key_cap, b_cap)};
 }
 
 // ---- lens undistortion (undistort.hip) ----

@@ -55,6 +55,7 @@ assert KEYPOINT_DTYPE.itemsize == 28
 # sift_match: one kept match of ratioMatches (query / train local to their segments)
 MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("distance", "<f4"), ("segment", "<i4")])
 assert MATCH_DTYPE.itemsize == 16
+JOIN_QUERY, JOIN_TRAIN = 0, 1  # SIFT_JOIN_*: the index of a record that names the shared view's keypoint
 
 
 class SiftError(RuntimeError):
@@ -197,6 +198,11 @@ def lib():
                                                      ctypes.c_double, vp, vp, vp, vp]),
             "sift_solve_pnp_segmented": (ip, [vp, pdbl, fp, pint, ip, ip, vp, pdbl, ip, ctypes.c_double, ip,
                                               ctypes.c_double, pdbl, pint, pint, vp]),
+            "sift_join_matches": (ip, [vp, ip, ip, vp, vp, vp, ip, ip, vp, vp, ip, vp, vp, vp, vp, vp]),
+            "sift_join_matches_segmented_device": (ip, [vp, vp, vp, ip, ip, vp, vp, vp, vp, ip, ip, vp, vp, vp, ip,
+                                                        ip, vp, vp, vp, vp, vp, ip, vp]),
+            "sift_join_matches_segmented": (ip, [vp, vp, vp, ip, ip, vp, vp, vp, vp, ip, ip, vp, vp, vp, ip, ip, vp,
+                                                 vp, vp, vp, vp, ip, vp]),
             "sift_undistort_batch_device": (ip, [vp, ip, ip, vp, ip, ip, sz, sz, vp, vp, vp, ip, ip, vp, ip, ip, sz, sz]),
             "sift_undistort": (ip, [vp, ip, ip, vp, ip, ip, sz, pdbl, pdbl, pdbl, vp, ip, ip]),
             "sift_undistort_points": (ip, [pdbl, pdbl, pdbl, ip, vp, vp, sz, ip]),
@@ -236,7 +242,8 @@ def lib():
                     "sift_triangulate_points_segmented_device", "sift_undistort_batch_device", "sift_undistort",
                     "sift_undistort_points", "sift_undistort_points_segmented_device",
                     "sift_undistort_points_segmented", "sift_solve_p3p", "sift_solve_pnp",
-                    "sift_solve_pnp_segmented_device", "sift_solve_pnp_segmented"}  # absent from older builds (A/B runs against a saved library)
+                    "sift_solve_pnp_segmented_device", "sift_solve_pnp_segmented", "sift_join_matches",
+                    "sift_join_matches_segmented_device", "sift_join_matches_segmented"}  # absent from older builds (A/B runs against a saved library)
         for name, (res, args) in sigs.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -1396,6 +1403,66 @@ class Context:
                         int(ni[b])))
         return out
 
+    # ---- a whole batch: the join of two match tables on a shared keypoint (2-D / 3-D rows) ---
+    def join_matches_segmented_device(self, a_ptr: int, a_offsets_ptr: int, a_cap: int, a_key_side: int,
+                                      a_xyz_ptr: int | None, b_ptr: int, b_offsets_ptr: int, b_cap: int,
+                                      b_key_side: int, b_xy_ptr: int | None, key_offsets_ptr: int, key_cap: int,
+                                      n_segments: int, j_cap: int, j_offsets_ptr: int,
+                                      xyz_out_ptr: int | None = None, xy_out_ptr: int | None = None,
+                                      a_row_ptr: int | None = None, b_row_ptr: int | None = None,
+                                      b_joined_ptr: int | None = None, a_mask_ptr: int | None = None,
+                                      b_mask_ptr: int | None = None):
+        """Device-pointer form (no sync) of joinMatches for every segment: segment s
+        joins A rows [a_offsets[s], a_offsets[s+1]) with B rows [b_offsets[s],
+        b_offsets[s+1]) on a key below key_offsets[s+1] - key_offsets[s] (offsets read
+        on the device and clamped to a_cap / b_cap / key_cap).  a_xyz_ptr [a_cap][3]
+        float64 and a_mask_ptr [a_cap] uint8 exactly as recover_pose_segmented_device
+        leaves xyz_ptr / mask_out_ptr; b_xy_ptr [b_cap][2] float32.  Outputs:
+        xyz_out_ptr [j_cap][3] float64, xy_out_ptr [j_cap][2] float32, a_row_ptr /
+        b_row_ptr [j_cap] int32 (absolute rows), b_joined_ptr [b_cap] uint8,
+        j_offsets_ptr [n_segments + 1] int32 (the last entry is the true total).
+        Consecutive frames of a batch, on ratio_matches_device's one table: b_ptr =
+        a_ptr, b_offsets_ptr = a_offsets_ptr + 4, a_key_side = JOIN_TRAIN, b_key_side =
+        JOIN_QUERY, b_xy_ptr = dst_xy_ptr, key_offsets_ptr = the keypoint offsets + 4,
+        n_segments = batch - 2; xyz_out_ptr, xy_out_ptr and j_offsets_ptr then feed
+        solve_pnp_segmented_device."""
+        vp = lambda p: ctypes.c_void_p(p or None)  # noqa: E731
+        self._check("sift_join_matches_segmented_device",
+                    self._L.sift_join_matches_segmented_device(
+                        self.h, vp(a_ptr), vp(a_offsets_ptr), a_cap, int(a_key_side), vp(a_mask_ptr), vp(a_xyz_ptr),
+                        vp(b_ptr), vp(b_offsets_ptr), b_cap, int(b_key_side), vp(b_mask_ptr), vp(b_xy_ptr),
+                        vp(key_offsets_ptr), key_cap, n_segments, vp(xyz_out_ptr), vp(xy_out_ptr), vp(a_row_ptr),
+                        vp(b_row_ptr), vp(b_joined_ptr), j_cap, vp(j_offsets_ptr)))
+
+    def joinMatchesSegmented(self, a, a_offsets, a_xyz, b, b_offsets, b_xy, key_offsets, a_key_side: int,
+                             b_key_side: int, a_mask=None, b_mask=None, j_cap: int | None = None,
+                             key_cap: int | None = None):
+        """joinMatches for every segment at once (host arrays): a / b MATCH_DTYPE
+        tables, a_xyz [len(a), 3], b_xy [len(b), 2], the three offset arrays
+        n_segments + 1 entries each, key_offsets the shared views' keypoint offsets
+        -> (xyz [n, 3], xy [n, 2], a_row [n], b_row [n], b_joined uint8[len(b)],
+        j_offsets [n_segments + 1]); rows are absolute, n = min(j_offsets[-1],
+        j_cap), j_cap defaults to len(b), key_cap (the keypoint count the key
+        offsets are clamped to) to the largest key offset."""
+        A, B, X, P, am, bm = _join_tables(a, a_xyz, b, b_xy, a_mask, b_mask)
+        ao, bo, ko = (np.ascontiguousarray(o, np.int32) for o in (a_offsets, b_offsets, key_offsets))
+        if ao.ndim != 1 or len(ao) < 1 or bo.shape != ao.shape or ko.shape != ao.shape:
+            raise ValueError("a_offsets, b_offsets and key_offsets must have n_segments + 1 entries each")
+        cap = len(B) if j_cap is None else int(j_cap)
+        key_cap = int(max(0, ko.max())) if key_cap is None else int(key_cap)
+        n = max(cap, 1)
+        xyz, xy = np.zeros((n, 3), np.float64), np.zeros((n, 2), np.float32)
+        ar, br = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        bj, jo = np.zeros(max(len(B), 1), np.uint8), np.zeros(len(ao), np.int32)
+        d = lambda v: None if v is None else v.ctypes.data  # noqa: E731
+        self._check("sift_join_matches_segmented",
+                    self._L.sift_join_matches_segmented(
+                        self.h, d(A), d(ao), len(A), int(a_key_side), d(am), d(X), d(B), d(bo), len(B),
+                        int(b_key_side), d(bm), d(P), d(ko), key_cap, len(ao) - 1, d(xyz), d(xy), d(ar), d(br), d(bj),
+                        cap, d(jo)))
+        m = min(int(jo[-1]), cap)
+        return xyz[:m], xy[:m], ar[:m], br[:m], bj[:len(B)], jo
+
     # ---- device batch API ------------------------------------------------
     def synth_images(self, out_ptr: int, batch: int, rows: int, cols: int, row_stride: int,
                      img_stride: int, seed_base: int = 0):
@@ -2026,6 +2093,40 @@ def solvePnPRansac(objectPoints, imagePoints, K, reprojectionError: float = 8.0,
         return None, None, np.zeros(n, np.uint8), 0
     P = pose.reshape(3, 4)
     return P[:, :3].copy(), P[:, 3].copy(), mout[:n], ni.value
+
+
+def _join_tables(a, a_xyz, b, b_xy, a_mask, b_mask):
+    """The two tables of a join as contiguous arrays, their row counts checked."""
+    A, B = np.ascontiguousarray(a, MATCH_DTYPE).reshape(-1), np.ascontiguousarray(b, MATCH_DTYPE).reshape(-1)
+    X = np.ascontiguousarray(a_xyz, np.float64).reshape(-1, 3)
+    P = np.ascontiguousarray(b_xy, np.float32).reshape(-1, 2)
+    am = None if a_mask is None else np.ascontiguousarray(a_mask, np.uint8).reshape(-1)
+    bm = None if b_mask is None else np.ascontiguousarray(b_mask, np.uint8).reshape(-1)
+    if len(X) != len(A) or len(P) != len(B):
+        raise ValueError("a_xyz needs one row per record of a, b_xy one per record of b")
+    if (am is not None and len(am) != len(A)) or (bm is not None and len(bm) != len(B)):
+        raise ValueError("a mask must have one byte per record")
+    return A, B, X, P, am, bm
+
+
+def joinMatches(a, a_xyz, b, b_xy, n_keys: int, a_key_side: int, b_key_side: int, a_mask=None, b_mask=None):
+    """The 2-D / 3-D rows of a new view from two match tables that share a view: table a (MATCH_DTYPE)
+    carries a_xyz [len(a), 3] by record (recoverPose's points, a_mask its mask), table b the new view's
+    pixel b_xy [len(b), 2] by record; a_key_side / b_key_side (JOIN_QUERY, JOIN_TRAIN) say which index of
+    a record names the shared view's keypoint, n_keys is that view's keypoint count.  Per key the unmasked
+    record of a with the smallest distance (then the lowest row) wins; every unmasked record of b whose
+    key has a winner joins, in b's order -> (xyz [n, 3], xy [n, 2], a_row [n], b_row [n], b_joined
+    uint8[len(b)]).  Host code in the library (include/sift_hip.h has the rule)."""
+    A, B, X, P, am, bm = _join_tables(a, a_xyz, b, b_xy, a_mask, b_mask)
+    n = max(len(B), 1)
+    xyz, xy = np.zeros((n, 3), np.float64), np.zeros((n, 2), np.float32)
+    ar, br, bj = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint8)
+    d = lambda v: None if v is None else v.ctypes.data  # noqa: E731
+    m = lib().sift_join_matches(d(A), len(A), int(a_key_side), d(am), d(X), d(B), len(B), int(b_key_side), d(bm), d(P),
+                                int(n_keys), d(xyz), d(xy), d(ar), d(br), d(bj))
+    if m < 0:
+        raise SiftError("sift_join_matches", m, "bad argument")
+    return xyz[:m], xy[:m], ar[:m], br[:m], bj[:len(B)]
 
 
 WARP_INVERSE_MAP = 16  # cv::WARP_INVERSE_MAP
